@@ -18,8 +18,13 @@ oracle -- bf16x2 (split weights in every weight product, forward and backward: g
 cpu_baseline: the fp32 CPU restatement of the same step (oracle/, "port") on a bounded sample of
 trajectories, timed on this host, plus the AR plumbing config (p = 50, M = 50, k = 50) at true size.
 
-Usage: python bench.py [--gpus N --steps K --warmup W]  (N > 1: launched by torch.distributed.run with
---gpus N, or started as plain `python bench.py --gpus N`, which spawns the N ranks itself)
+A plain run sets up, warms up, times the K steps (the live HIP-event figures above ride on those same steps) and
+prints the result line.  --full adds what takes runs of its own: parity_precision, cpu_baseline and family_lines
+(each still switchable with its own option).  --dump-outputs DIR writes what the last timed step returned (the
+elbo_step dict) and left behind (flat parameters and gradient) as DIR/<name>.npy.
+
+Usage: python bench.py [--gpus N --steps K --warmup W --full --dump-outputs DIR]  (N > 1: launched by
+torch.distributed.run with --gpus N, or started as plain `python bench.py --gpus N`, which spawns the N ranks itself)
 """
 from __future__ import annotations
 
@@ -190,6 +195,29 @@ def cpu_baseline_ar_plumbing(args):
                       f"restatement, median of {n} steps after 2 warm-up"}
 
 
+DUMP_MAX_ELEMS = 1 << 20  # per dumped array: 4 MiB of float32, so the dozen arrays of a step stay far below 64 MB
+
+
+def dump_outputs(path, arrays):
+    """Write each tensor / number of `arrays` as path/<name>.npy (float32, or float64 where the value is).  An
+    array of more than DUMP_MAX_ELEMS elements is written as a fixed sample: the elements at the sorted flat
+    (row-major) indices np.random.default_rng(0).integers(0, numel, DUMP_MAX_ELEMS), the same from run to run."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, v in arrays.items():
+        if v is None:
+            continue
+        if not isinstance(v, torch.Tensor):
+            v = torch.as_tensor(v)
+        v = v.detach()
+        if v.numel() > DUMP_MAX_ELEMS:
+            flat = np.sort(np.random.default_rng(0).integers(0, v.numel(), DUMP_MAX_ELEMS))
+            idx = tuple(torch.from_numpy(i).to(v.device) for i in np.unravel_index(flat, tuple(v.shape)))
+            v = v[idx]
+        v = v.to(torch.float64 if v.dtype == torch.float64 else torch.float32)
+        np.save(os.path.join(path, f"{name}.npy"), v.cpu().numpy())
+
+
 MODEL_DEFAULTS = {  # SURVEY.md §8d configs: per-GPU batch, T, kernel_len
     "ar": (65536, 5000, 8), "sv": (16384, 1508, 50), "lv": (16384, 5000, 20), "fhn": (8192, 2000, 20)}
 
@@ -277,6 +305,14 @@ def parse_args(argv=None):
                          "reductions and the optimizer are fp32 throughout")
     ap.add_argument("--graph", action="store_true",
                     help="replay the step as a captured HIP graph (viforssms_amd.graph; needs warmup >= 3)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the parity-precision lines, the CPU "
+                         "baseline and the other families (--parity-line / --cpu-baseline / --families, each 'auto' "
+                         "by default, take effect only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs (the elbo_step dict, the flat "
+                         "parameters and gradient it left; rank 0's shard) as DIR/<name>.npy, arrays above 2^20 "
+                         "elements as a fixed seeded sample")
     ap.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto")
     ap.add_argument("--fuse", choices=["on", "off"], default="on",
                     help="AR at bf16 / bf16x3: run the last flow fused with the ELBO terms (vissm_flow_ar_elbo_fused)")
@@ -318,9 +354,8 @@ def measure(args, ctx, dev, parity_line: bool):
     def step(i):
         starts = model.select_windows()
         if args.graph:
-            model.graphed_step(starts, i)
-        else:
-            model.elbo_step(model.batch_for(starts), i)
+            return model.graphed_step(starts, i)
+        return model.elbo_step(model.batch_for(starts), i)
 
     if args.graph:
         args.warmup = max(args.warmup, 3)  # two eager warm-up steps, then the capture
@@ -330,7 +365,8 @@ def measure(args, ctx, dev, parity_line: bool):
 
     def timed(first_step):
         """Warm-up, then EXACTLY args.steps timed steps between barrier + synchronize on both sides;
-        max over ranks.  Returns (elapsed_s, {profile kind: (ms, launches, algorithmic bytes)})."""
+        max over ranks.  Returns (elapsed_s, {profile kind: (ms, launches, algorithmic bytes)}, the last timed
+        step's outputs)."""
         for i in range(args.warmup):
             step(first_step + i)
         torch.cuda.synchronize()
@@ -339,8 +375,10 @@ def measure(args, ctx, dev, parity_line: bool):
         lib.vissm_profile_reset()
         lib.vissm_profile_enable(1)
         t0 = time.perf_counter()
+        out = None
         for i in range(args.steps):
-            step(first_step + args.warmup + i)
+            out = None  # the previous step's outputs are released before the next step allocates its own
+            out = step(first_step + args.warmup + i)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -357,9 +395,12 @@ def measure(args, ctx, dev, parity_line: bool):
             _lib.check(lib.vissm_profile_bytes(kind, ctypes.byref(nbytes)), "profile_bytes")
             prof[kind] = (tot.value, cnt.value, nbytes.value)
         lib.vissm_profile_reset()
-        return elapsed, prof
+        return elapsed, prof, out
 
-    elapsed, prof = timed(0)
+    elapsed, prof, out = timed(0)
+    if args.dump_outputs and rank == 0 and out is not None:
+        dump_outputs(args.dump_outputs, {**out, "params": model.store.flat, "grad": model.store.grad})
+    del out
     # parity-precision lines: the same step at the precisions that hold the per-sample ELBO within
     # north_star's 1e-4 of the float64 oracle, timed the same way
     px = None
@@ -383,7 +424,7 @@ def measure(args, ctx, dev, parity_line: bool):
                  "every flow product split bf16 hi+lo (three MFMAs): ELBO within 1e-4 and gradient within 1e-3 of "
                  "the float64 oracle")):
             model.engine.precision = mode
-            px_elapsed, px_prof = timed(args.warmup + args.steps)
+            px_elapsed, px_prof = timed(args.warmup + args.steps)[:2]
             b_ms, b_n, _ = px_prof[_lib.PROF_FLOW_BWD]
             f_ms, f_n, _ = px_prof[_lib.PROF_FLOW_FWD]
             px.append({"dtype": name, "value": world * args.B * args.M * args.steps / px_elapsed,
@@ -545,13 +586,13 @@ def main():
 
     ctx = init_distributed()
     dev = torch.device("cuda", torch.cuda.current_device())
-    res, model, meta = measure(args, ctx, dev, parity_line=args.parity_line == "auto")
-    if args.cpu_baseline == "auto" and ctx.world == 1 and args.model == "ar" and ctx.rank == 0:
+    res, model, meta = measure(args, ctx, dev, parity_line=args.full and args.parity_line == "auto")
+    if args.full and args.cpu_baseline == "auto" and ctx.world == 1 and args.model == "ar" and ctx.rank == 0:
         res["cpu_baseline"] = cpu_baseline(args, *meta["ar_data"])
         res["cpu_baseline"]["ar_plumbing"] = cpu_baseline_ar_plumbing(args)
     else:
         res["cpu_baseline"] = None
-    if args.families == "auto" and args.model == "ar" and not args.graph:
+    if args.full and args.families == "auto" and args.model == "ar" and not args.graph:
         del model
         torch.cuda.empty_cache()
         res["family_lines"] = family_lines(args, ctx, dev)

@@ -11,7 +11,7 @@ timeout -k 10 900 python -u -m pytest tests/test_gpu_elbo_models.py tests/test_g
   --timeout 300 --timeout-method thread > "$OUT/pytest.log" 2>&1; rc=$?
 tail -4 "$OUT/pytest.log"; fault $rc
 echo "== bench full"; date
-timeout -k 10 900 python bench.py > "$OUT/bench_full.log" 2>&1 || { tail -20 "$OUT/bench_full.log"; exit 3; }
+timeout -k 10 900 python bench.py --full > "$OUT/bench_full.log" 2>&1 || { tail -20 "$OUT/bench_full.log"; exit 3; }
 tail -1 "$OUT/bench_full.log" | cut -c1-400
 echo "== rocprofv3 kernel trace (AR step, LV / FHN steps)"; date
 cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats -T -d "$OUT/prof" -o bench --output-format csv -- python "$ROOT/bench.py" --steps 3 --warmup 1 --cpu-baseline off --parity-line off --families off > "$OUT/prof.log" 2>&1 || { tail -20 "$OUT/prof.log"; exit 4; }

@@ -14,7 +14,7 @@ echo "== smoke"; timeout -k 10 300 python -c "import __graft_entry__ as g; g.smo
 tail -2 "$OUT/smoke.log"; fault $rc
 fi
 echo "== bench full"; date
-timeout -k 10 900 python bench.py $BENCH_ARGS > "$OUT/bench_full.log" 2>&1 || { tail -20 "$OUT/bench_full.log"; exit 3; }
+timeout -k 10 900 python bench.py --full $BENCH_ARGS > "$OUT/bench_full.log" 2>&1 || { tail -20 "$OUT/bench_full.log"; exit 3; }
 tail -1 "$OUT/bench_full.log"
 echo "== rocprofv3 kernel trace"; date
 cd /tmp && timeout -k 10 900 rocprofv3 --kernel-trace --stats -T -d "$OUT/prof" -o bench --output-format csv -- python "$ROOT/bench.py" --steps 3 --warmup 1 --cpu-baseline off --parity-line off --families off $BENCH_ARGS > "$OUT/prof.log" 2>&1 || { tail -20 "$OUT/prof.log"; exit 4; }
