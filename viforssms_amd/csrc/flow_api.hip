@@ -67,6 +67,16 @@ int flow5_ar_fused_fz(const VissmFlowDesc* d, const VissmFlowParams* w, const fl
 #ifndef VISSM_FUSED_TU
 #define VISSM_FUSED_TU 1
 #endif
+// The first flow's backward (no du: its input is the base noise) on the bf16 two-sample AR kernel runs in that build
+// too: bwd2_kernel<FZ = false, DU = false> 17.80 -> 17.26 ms per AR-cfg launch under the trackers, no scratch in
+// either build, the same arithmetic (the du variant of the middle flows stays in flow_v5.hip's build: 20.40 -> 20.49
+// there; profiles/r07/step1_ab.txt).  VISSM_NODU_TU=0: the flow_v5.hip build (A/B)
+bool flow5_bwd_two_sample_bf16(const VissmFlowDesc* d);
+int flow5_bwd_fz(const VissmFlowDesc*, const VissmFlowParams*, const float*, const float*, const int32_t*, const float*,
+                 const float*, const float*, float*, float*, float*, const VissmFlowGrads*, void*, size_t, hipStream_t);
+#ifndef VISSM_NODU_TU
+#define VISSM_NODU_TU 1
+#endif
 #if VISSM_FUSED_TU
 #define FUSED_API(name) name##_fz
 #else
@@ -185,6 +195,8 @@ int vissm_flow_bwd(const VissmFlowDesc* d, const VissmFlowParams* w, const float
                   "flow_bwd: bn needs bn_g/bn_b pointers");
   VISSM_CHECK_ARG(d->n_win == 1 || win, "flow_bwd: n_win > 1 needs win[]");
   hipStream_t st = as_stream(stream);
+  if (VISSM_NODU_TU && !du && use_v5(d) && flow5_bwd_two_sample_bf16(d))  // same workspace layout in either build
+    return flow5_bwd_fz(d, w, u, C, win, theta_term, du_next, dlogsig, du, dC, dtheta_term, gr, workspace, ws_bytes, st);
   if (use_v5(d))
     return (use_nh3(d) ? flow5_bwd_nh3 : use_nh3s(d) ? flow5_bwd_nh3s : flow5_bwd)(d, w, u, C, win, theta_term,
                                                                                     du_next, dlogsig, du, dC, dtheta_term,

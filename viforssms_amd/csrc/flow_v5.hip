@@ -3172,6 +3172,13 @@ int VISSM_FLOW5_API(flow5_fwd)(const VissmFlowDesc* d, const VissmFlowParams* w,
   return launch_reduce_rows(ws.ls_slab, logsig, g.n_chunks, d->B, st);
 }
 
+// whether flow5_bwd runs this descriptor on the bf16 two-sample AR kernel (bwd2_kernel, single-bf16 products):
+// flow_api.hip sends that shape's backward without du to the build of flow_v5f.hip
+bool VISSM_FLOW5_API(flow5_bwd_two_sample_bf16)(const VissmFlowDesc* d) {
+  const Geom g = geom(d, true);
+  return np_of(d) == 1 && !bwd2n_ok(d, g) && bwd2_ok(d, g);
+}
+
 int VISSM_FLOW5_API(flow5_bwd)(const VissmFlowDesc* d, const VissmFlowParams* w, const float* u, const float* C, const int32_t* win,
               const float* theta_term, const float* du_next, const float* dlogsig, float* du, float* dC,
               float* dtheta_term, const VissmFlowGrads* gr, void* workspace, size_t ws_bytes, hipStream_t st) {
