@@ -6,7 +6,7 @@ Compiles the unit's device code for gfx950 with the command line the Makefile us
 host; nothing is linked or run.
 
 usage: python scripts/kernel_resources.py flow_v5.hip [--filter REGEX] [--make-arg VAR=VALUE ...]
-(`make -C viforssms_amd/csrc resources` writes the tables of flow_v5.hip and flow_v5f.hip to profiles/r07/resources/)
+(`make -C viforssms_amd/csrc resources` writes the tables of the four flow_v5 units to profiles/r08/resources/)
 """
 import argparse
 import os

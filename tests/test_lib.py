@@ -308,6 +308,30 @@ def test_asm_mfma_accumulators_hazard_free():
     assert "bwd2n_kernel" in r.stdout
 
 
+def test_flow5_units_share_no_kernel_stub():
+    """The four units of the bf16 flow (flow_v5*.hip) keep their kernel templates in per-unit namespaces: the same
+    instantiation is built in two units on purpose, with different flags (bwd2n_kernel in flow_v5n / flow_v5s,
+    bwd2_kernel in flow_v5 / flow_v5f), and template kernels' host stubs are weak symbols -- in a shared namespace the
+    linker would keep one copy and tests/test_gpu_vgpr_form.py would compare a build with itself.  So no kernel host
+    stub may be defined in more than one of build/flow_v5*.o."""
+    import glob
+    import shutil
+    import subprocess
+    objs = sorted(glob.glob(os.path.join(ROOT, "viforssms_amd", "csrc", "build", "flow_v5*.o")))
+    assert [os.path.basename(o) for o in objs] == ["flow_v5.o", "flow_v5f.o", "flow_v5n.o", "flow_v5s.o"], objs
+    nm = next((t for t in ("/opt/rocm/llvm/bin/llvm-nm", shutil.which("llvm-nm"), shutil.which("nm"))
+               if t and os.path.exists(t)), None)
+    assert nm, "no nm (llvm or binutils) on this host"
+    owner = {}
+    for o in objs:
+        out = subprocess.run([nm, "--defined-only", o], capture_output=True, text=True, check=True).stdout
+        stubs = {l.split()[-1] for l in out.splitlines() if "__device_stub__" in l}
+        assert stubs, f"{o}: no kernel host stub found"
+        for s in stubs:
+            assert s not in owner, f"{s} is defined in {owner[s]} and {os.path.basename(o)}"
+            owner[s] = os.path.basename(o)
+
+
 def test_agpr_audit_detects_unpadded_reads(tmp_path):
     """scripts/check_agpr_asm.py is not vacuous: on a synthetic kernel it flags a compiler read of an AGPR an asm MFMA
     just wrote, across a fall-through and a branch edge, and passes once a drain statement sits in between."""

@@ -4,7 +4,7 @@
 // flow4 (register-resident weights, latency hiding) for one hidden layer, flow2 for
 // deeper heads (LV / SV / FHN), where flow4's register-resident weights do not apply
 // and it measured slower (LV-like shape: 64 vs 76 ms bwd).  No process state.
-#include "common.hpp"
+#include "flow5_api.hpp"
 
 #include <cstdlib>
 
@@ -14,8 +14,6 @@ size_t flow2_workspace_size(const VissmFlowDesc* d, int backward);
 size_t flow4_workspace_size(const VissmFlowDesc* d, int backward);
 void flow2_geometry(const VissmFlowDesc* d, int backward, int32_t* out);
 void flow4_geometry(const VissmFlowDesc* d, int backward, int32_t* out);
-void flow5_geometry(const VissmFlowDesc* d, int which, int32_t* out);
-void flow5_geometry_nh3(const VissmFlowDesc* d, int which, int32_t* out);
 int flow4_fwd(const VissmFlowDesc*, const VissmFlowParams*, const float*, const float*, const int32_t*, const float*,
               float*, float*, void*, size_t, hipStream_t);
 int flow4_bwd(const VissmFlowDesc*, const VissmFlowParams*, const float*, const float*, const int32_t*, const float*,
@@ -24,64 +22,6 @@ int flow2_fwd(const VissmFlowDesc*, const VissmFlowParams*, const float*, const 
               float*, float*, void*, size_t, hipStream_t);
 int flow2_bwd(const VissmFlowDesc*, const VissmFlowParams*, const float*, const float*, const int32_t*, const float*,
               const float*, const float*, float*, float*, float*, const VissmFlowGrads*, void*, size_t, hipStream_t);
-
-bool flow5_supports(const VissmFlowDesc* d);
-size_t flow5_workspace_size(const VissmFlowDesc* d, int backward);
-int flow5_fwd(const VissmFlowDesc*, const VissmFlowParams*, const float*, const float*, const int32_t*, const float*,
-              float*, float*, void*, size_t, hipStream_t);
-int flow5_bwd(const VissmFlowDesc*, const VissmFlowParams*, const float*, const float*, const int32_t*, const float*,
-              const float*, const float*, float*, float*, float*, const VissmFlowGrads*, void*, size_t, hipStream_t);
-
-// the same kernels built without the SLP vectorizer (flow_v5n.hip): the three-hidden-layer shapes
-bool flow5_supports_nh3(const VissmFlowDesc* d);
-size_t flow5_workspace_size_nh3(const VissmFlowDesc* d, int backward);
-int flow5_fwd_nh3(const VissmFlowDesc*, const VissmFlowParams*, const float*, const float*, const int32_t*,
-                  const float*, float*, float*, void*, size_t, hipStream_t);
-int flow5_bwd_nh3(const VissmFlowDesc*, const VissmFlowParams*, const float*, const float*, const int32_t*,
-                  const float*, const float*, const float*, float*, float*, float*, const VissmFlowGrads*, void*,
-                  size_t, hipStream_t);
-
-// and for k > 32 at three hidden layers (flow_v5s.hip)
-void flow5_geometry_nh3s(const VissmFlowDesc* d, int which, int32_t* out);
-size_t flow5_workspace_size_nh3s(const VissmFlowDesc* d, int backward);
-int flow5_fwd_nh3s(const VissmFlowDesc*, const VissmFlowParams*, const float*, const float*, const int32_t*,
-                   const float*, float*, float*, void*, size_t, hipStream_t);
-int flow5_bwd_nh3s(const VissmFlowDesc*, const VissmFlowParams*, const float*, const float*, const int32_t*,
-                   const float*, const float*, const float*, float*, float*, float*, const VissmFlowGrads*, void*,
-                   size_t, hipStream_t);
-
-bool flow5_ar_fused_supports(const VissmFlowDesc* d);
-size_t flow5_ar_fused_workspace_size(const VissmFlowDesc* d);
-int flow5_ar_fused(const VissmFlowDesc* d, const VissmFlowParams* w, const float* u, const float* C, const int32_t* win,
-                   const float* theta_term, const float* theta, const float* obs, const float* obs_bin, float obs_std,
-                   float scale, float* x, float* logsig, float* du, float* dC, float* dtheta_term,
-                   const VissmFlowGrads* gr, void* workspace, size_t ws_bytes, hipStream_t st);
-// the same, built with the scheduler's register-pressure trackers (flow_v5f.hip): the fused flow's kernels run there
-// (VISSM_FUSED_TU=0: the flow_v5.hip build, A/B)
-bool flow5_ar_fused_supports_fz(const VissmFlowDesc* d);
-size_t flow5_ar_fused_workspace_size_fz(const VissmFlowDesc* d);
-int flow5_ar_fused_fz(const VissmFlowDesc* d, const VissmFlowParams* w, const float* u, const float* C,
-                      const int32_t* win, const float* theta_term, const float* theta, const float* obs,
-                      const float* obs_bin, float obs_std, float scale, float* x, float* logsig, float* du, float* dC,
-                      float* dtheta_term, const VissmFlowGrads* gr, void* workspace, size_t ws_bytes, hipStream_t st);
-#ifndef VISSM_FUSED_TU
-#define VISSM_FUSED_TU 1
-#endif
-// The first flow's backward (no du: its input is the base noise) on the bf16 two-sample AR kernel runs in that build
-// too: bwd2_kernel<FZ = false, DU = false> 17.80 -> 17.26 ms per AR-cfg launch under the trackers, no scratch in
-// either build, the same arithmetic (the du variant of the middle flows stays in flow_v5.hip's build: 20.40 -> 20.49
-// there; profiles/r07/step1_ab.txt).  VISSM_NODU_TU=0: the flow_v5.hip build (A/B)
-bool flow5_bwd_two_sample_bf16(const VissmFlowDesc* d);
-int flow5_bwd_fz(const VissmFlowDesc*, const VissmFlowParams*, const float*, const float*, const int32_t*, const float*,
-                 const float*, const float*, float*, float*, float*, const VissmFlowGrads*, void*, size_t, hipStream_t);
-#ifndef VISSM_NODU_TU
-#define VISSM_NODU_TU 1
-#endif
-#if VISSM_FUSED_TU
-#define FUSED_API(name) name##_fz
-#else
-#define FUSED_API(name) name
-#endif
 
 static bool use_flow4(const VissmFlowDesc* d) { return d->n_hidden <= 1; }
 
@@ -110,13 +50,16 @@ static int validate(const VissmFlowDesc* d) {
 // cover the shape; anything else runs the exact-fp32 kernels (never less precise
 // than requested).
 static bool use_v5(const VissmFlowDesc* d) { return d->precision != VISSM_PREC_FP32 && flow5_supports(d); }
-// three hidden layers on one window with the two-sample backward's k (LV, FHN: k <= 24; SV: 32 < k <= 64, stride 1): the
+// The bf16 kernels ship from four translation units (flow5_api.hpp), each compiling only the kernels of the shapes
+// the predicates below send to it, with its own compiler flags; workspace size and geometry are functions of the
+// descriptor alone, the same for every unit.  This file is the only place where the unit is chosen.
+// Three hidden layers on one window with the two-sample backward's k (LV, FHN: k <= 24; SV: 32 < k <= 64, stride 1): the
 // builds without the SLP vectorizer (LV-cfg backward 18.1 -> 16.8 ms, FHN 3.7 -> 3.5, SV 7.2 -> 6.7 ms per launch),
 // k <= 24 in flow_v5n.hip (also VGPR-form MFMAs and AGPR accumulators: LV 16.6 -> 14.6 ms), k > 32 in flow_v5s.hip.
 // The one-sample three-layer kernel (several windows) measured slower without the vectorizer (SV: 10.3 -> 10.8 ms).
-// VISSM_NH3_DEFAULT_FORM=1 sends the k <= 24 shapes to flow_v5s.hip's build as well (the same source without the
-// VGPR-form flag and the asm accumulators): tests/test_gpu_vgpr_form.py checks that flow_v5n.hip's kernels compute what
-// that build computes at every shape they ship for -- the flag miscompiled SV's k = 50 du variant
+// VISSM_NH3_DEFAULT_FORM=1 sends the k <= 24 shapes to flow_v5s.hip's build of the same kernels (no VGPR-form flag,
+// no asm accumulators): tests/test_gpu_vgpr_form.py checks that flow_v5n.hip's kernels compute what that build
+// computes at every shape they ship for -- the flag miscompiled SV's k = 50 du variant
 static bool nh3_default_form() {
   const char* e = std::getenv("VISSM_NH3_DEFAULT_FORM");
   return e && e[0] == '1';
@@ -128,6 +71,19 @@ static bool use_nh3s(const VissmFlowDesc* d) {
   return d->n_hidden == 3 && d->n_win == 1 && d->k <= 64 &&
          ((d->k > 32 && !d->stride2) || (d->k <= 24 && nh3_default_form()));
 }
+// The first flow's backward (no du: its input is the base noise) on the bf16 two-sample AR kernel runs in the build
+// with the scheduler's register-pressure trackers (flow_v5f.hip), as the fused last flow does: bwd2_kernel<FZ = false,
+// DU = false> 17.80 -> 17.26 ms per AR-cfg launch there, the same arithmetic and workspace layout (the du variant of
+// the middle flows stays in flow_v5.hip's build: 20.40 -> 20.49 under the trackers; profiles/r07/step1_ab.txt)
+static bool use_nodu_f(const VissmFlowDesc* d, const float* du) { return !du && flow5_bwd_two_sample_bf16(d); }
+
+// the unit whose kernels run a descriptor of the bf16 kernels (use_v5)
+static Flow5Fwd* v5_fwd(const VissmFlowDesc* d) {
+  return use_nh3(d) ? flow5n_fwd : use_nh3s(d) ? flow5s_fwd : flow5_fwd;
+}
+static Flow5Bwd* v5_bwd(const VissmFlowDesc* d, const float* du) {
+  return use_nodu_f(d, du) ? flow5f_bwd : use_nh3(d) ? flow5n_bwd : use_nh3s(d) ? flow5s_bwd : flow5_bwd;
+}
 
 }  // namespace vissm
 
@@ -137,9 +93,7 @@ extern "C" {
 
 size_t vissm_flow_workspace_size(const VissmFlowDesc* d, int32_t backward) {
   if (validate(d) != VISSM_OK) return 0;
-  if (use_v5(d))
-    return use_nh3(d) ? flow5_workspace_size_nh3(d, backward)
-         : use_nh3s(d) ? flow5_workspace_size_nh3s(d, backward) : flow5_workspace_size(d, backward);
+  if (use_v5(d)) return flow5_workspace_size(d, backward);
   return use_flow4(d) ? flow4_workspace_size(d, backward) : flow2_workspace_size(d, backward);
 }
 
@@ -151,7 +105,7 @@ int vissm_flow_geometry(const VissmFlowDesc* d, int32_t which, int32_t* out) {
     VISSM_CHECK_ARG(flow5_ar_fused_supports(d), "flow_geometry: the descriptor has no fused AR(1) last flow");
     flow5_geometry(d, 2, out);
   } else if (use_v5(d)) {
-    (use_nh3(d) ? flow5_geometry_nh3 : use_nh3s(d) ? flow5_geometry_nh3s : flow5_geometry)(d, which, out);
+    flow5_geometry(d, which, out);
   } else {
     (use_flow4(d) ? flow4_geometry : flow2_geometry)(d, which, out);
   }
@@ -171,9 +125,7 @@ int vissm_flow_fwd(const VissmFlowDesc* d, const VissmFlowParams* w, const float
   VISSM_CHECK_ARG(d->precision != VISSM_PREC_BF16X2_BF16,
                   "flow_fwd: VISSM_PREC_BF16X2_BF16 is a precision of vissm_flow_ar_elbo_fused only");
   hipStream_t st = as_stream(stream);
-  if (use_v5(d))
-    return (use_nh3(d) ? flow5_fwd_nh3 : use_nh3s(d) ? flow5_fwd_nh3s : flow5_fwd)(d, w, u, C, win, theta_term, u_next,
-                                                                                    logsig, workspace, ws_bytes, st);
+  if (use_v5(d)) return v5_fwd(d)(d, w, u, C, win, theta_term, u_next, logsig, workspace, ws_bytes, st);
   if (use_flow4(d)) return flow4_fwd(d, w, u, C, win, theta_term, u_next, logsig, workspace, ws_bytes, st);
   return flow2_fwd(d, w, u, C, win, theta_term, u_next, logsig, workspace, ws_bytes, st);
 }
@@ -195,12 +147,9 @@ int vissm_flow_bwd(const VissmFlowDesc* d, const VissmFlowParams* w, const float
                   "flow_bwd: bn needs bn_g/bn_b pointers");
   VISSM_CHECK_ARG(d->n_win == 1 || win, "flow_bwd: n_win > 1 needs win[]");
   hipStream_t st = as_stream(stream);
-  if (VISSM_NODU_TU && !du && use_v5(d) && flow5_bwd_two_sample_bf16(d))  // same workspace layout in either build
-    return flow5_bwd_fz(d, w, u, C, win, theta_term, du_next, dlogsig, du, dC, dtheta_term, gr, workspace, ws_bytes, st);
   if (use_v5(d))
-    return (use_nh3(d) ? flow5_bwd_nh3 : use_nh3s(d) ? flow5_bwd_nh3s : flow5_bwd)(d, w, u, C, win, theta_term,
-                                                                                    du_next, dlogsig, du, dC, dtheta_term,
-                                                                                    gr, workspace, ws_bytes, st);
+    return v5_bwd(d, du)(d, w, u, C, win, theta_term, du_next, dlogsig, du, dC, dtheta_term, gr, workspace, ws_bytes,
+                         st);
   if (use_flow4(d))
     return flow4_bwd(d, w, u, C, win, theta_term, du_next, dlogsig, du, dC, dtheta_term, gr, workspace, ws_bytes, st);
   return flow2_bwd(d, w, u, C, win, theta_term, du_next, dlogsig, du, dC, dtheta_term, gr, workspace, ws_bytes, st);
@@ -212,12 +161,12 @@ int32_t vissm_flow_kernel_precision(const VissmFlowDesc* d) {
 }
 
 int32_t vissm_flow_ar_elbo_fused_supported(const VissmFlowDesc* d) {
-  return (validate(d) == VISSM_OK && FUSED_API(flow5_ar_fused_supports)(d)) ? 1 : 0;
+  return (validate(d) == VISSM_OK && flow5_ar_fused_supports(d)) ? 1 : 0;
 }
 
 size_t vissm_flow_ar_elbo_fused_workspace_size(const VissmFlowDesc* d) {
   if (!vissm_flow_ar_elbo_fused_supported(d)) return 0;
-  return FUSED_API(flow5_ar_fused_workspace_size)(d);
+  return flow5_ar_fused_workspace_size(d);
 }
 
 int vissm_flow_ar_elbo_fused(const VissmFlowDesc* d, const VissmFlowParams* w, const float* u, const float* C,
@@ -227,7 +176,7 @@ int vissm_flow_ar_elbo_fused(const VissmFlowDesc* d, const VissmFlowParams* w, c
                              size_t ws_bytes, void* stream) {
   int rc = validate(d);
   if (rc) return rc;
-  VISSM_CHECK_ARG(FUSED_API(flow5_ar_fused_supports)(d),
+  VISSM_CHECK_ARG(flow5_ar_fused_supports(d),
                   "flow_ar_elbo_fused: needs bf16 / bf16x3 (k <= 32) or bf16x2 / bf16x2_bf16 (k <= 8, one window), one hidden "
                   "layer, no BN, "
                   "stride 1");
@@ -238,8 +187,8 @@ int vissm_flow_ar_elbo_fused(const VissmFlowDesc* d, const VissmFlowParams* w, c
   VISSM_CHECK_ARG(obs_std > 0.f, "flow_ar_elbo_fused: obs_std must be positive");
   VISSM_CHECK_ARG(d->out_pitch == 0 || d->out_pitch == d->L - d->k, "flow_ar_elbo_fused: x is written dense (out_pitch "
                   "%d must be 0 or L - k)", d->out_pitch);
-  return FUSED_API(flow5_ar_fused)(d, w, u, C, win, theta_term, theta, obs, obs_bin, obs_std, scale, x, logsig, du,
-                                   dC, dtheta_term, gr, workspace, ws_bytes, as_stream(stream));
+  return flow5f_ar_fused(d, w, u, C, win, theta_term, theta, obs, obs_bin, obs_std, scale, x, logsig, du, dC, dtheta_term,
+                         gr, workspace, ws_bytes, as_stream(stream));
 }
 
 }  // extern "C"

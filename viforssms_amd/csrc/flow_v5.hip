@@ -39,13 +39,19 @@
 // runs fwd2_kernel.  The AR kernels take the theta term folded into their layer-0 product when the caller passes the
 // theta branch's factors (VissmFlowParams.theta_rank); the fused last AR flow also runs at bf16x2 (split-weight
 // recompute).  Everything else runs on flow_v4 / flow_v2 (exact fp32).
-#include "common.hpp"
+//
+// Translation units.  Compiled as itself this file is the base unit (namespace flow5, the launch functions at its
+// end).  flow_v5n.hip, flow_v5s.hip and flow_v5f.hip define VISSM_FLOW5_NS and include it for the kernel templates
+// and the shared host code, then add launch functions of their own; each unit is built with its own compiler flags
+// (Makefile) and instantiates only the kernels flow_api.hip sends to it (flow5_api.hpp lists the units).  Everything
+// here sits in the unit's own namespace vissm::VISSM_FLOW5_NS: kernel templates and their host stubs are weak symbols,
+// and the same instantiation exists in two units on purpose with different flags (bwd2n_kernel in flow_v5n.hip and
+// flow_v5s.hip, bwd2_kernel in flow_v5.hip and flow_v5f.hip) -- in a shared namespace the linker would keep one copy.
+#include "flow5_api.hpp"
 
-// flow_v5n.hip compiles this file a second time, without the SLP vectorizer, under its own namespace and entry
-// point names: the three-hidden-layer shapes (LV / SV / FHN) dispatch there (flow_api.hip)
 #ifndef VISSM_FLOW5_NS
 #define VISSM_FLOW5_NS flow5
-#define VISSM_FLOW5_API(name) name
+#define VISSM_FLOW5_BASE_UNIT 1
 #endif
 
 #include <cstdlib>
@@ -3000,83 +3006,6 @@ static bool fwd2_ok(const VissmFlowDesc* d, const Geom& g) {
   return d->n_hidden == 3 && d->precision == VISSM_PREC_BF16;
 }
 
-}  // namespace VISSM_FLOW5_NS
-
-using namespace VISSM_FLOW5_NS;
-
-bool VISSM_FLOW5_API(flow5_supports)(const VissmFlowDesc* d) {
-  // one hidden layer (AR): bf16 and bf16x3 (k <= 32: hi + lo images in LDS); three hidden layers
-  // with or without BN (LV / SV / FHN heads): bf16
-  if (d->H > kMaxH || d->k > 64) return false;
-  if (d->precision == VISSM_PREC_BF16) return d->n_hidden == 1 || d->n_hidden == 3;
-  if (d->precision == VISSM_PREC_BF16X3) return d->n_hidden == 1 && d->k <= 32;
-  if (d->precision == VISSM_PREC_BF16X2) return d->n_hidden == 1 && d->k <= 32;
-  return false;
-}
-
-size_t VISSM_FLOW5_API(flow5_workspace_size)(const VissmFlowDesc* d, int backward) {
-  Geom g = geom(d, backward != 0);
-  return ws_layout(d, g, backward != 0, nullptr, nullptr);
-}
-
-// which: 0 forward, 1 backward, 2 the fused last AR flow (15 outputs per 16-column tile)
-void VISSM_FLOW5_API(flow5_geometry)(const VissmFlowDesc* d, int which, int32_t* out) {
-  const int po = which == 2 ? P - 1 : P;
-  Geom g = geom(d, which != 0, po);
-  out[0] = po; out[1] = g.CH / po; out[2] = g.n_chunks; out[3] = g.n_groups;
-}
-
-#define FLOW5_DISPATCH(KERNEL, NHd, JB, NP, ...)                                                  \
-  do {                                                                                             \
-    if (NP == 3) {                                                                                 \
-      if (JB == 1) hipLaunchKernelGGL((KERNEL<1, 1, 1, 3>), __VA_ARGS__);                           \
-      else hipLaunchKernelGGL((KERNEL<1, 1, 2, 3>), __VA_ARGS__);                                   \
-    } else if (NP == 2) {                                                                          \
-      if (JB == 1) hipLaunchKernelGGL((KERNEL<1, 1, 1, 2>), __VA_ARGS__);                           \
-      else hipLaunchKernelGGL((KERNEL<1, 1, 2, 2>), __VA_ARGS__);                                   \
-    } else if (NHd == 1) {                                                                         \
-      switch (JB) {                                                                                \
-        case 1: hipLaunchKernelGGL((KERNEL<1, 1, 1, 1>), __VA_ARGS__); break;                       \
-        case 2: hipLaunchKernelGGL((KERNEL<1, 1, 2, 1>), __VA_ARGS__); break;                       \
-        case 3: hipLaunchKernelGGL((KERNEL<1, 2, 3, 1>), __VA_ARGS__); break;                       \
-        default: hipLaunchKernelGGL((KERNEL<1, 2, 4, 1>), __VA_ARGS__); break;                      \
-      }                                                                                            \
-    } else {                                                                                       \
-      switch (JB) {                                                                                \
-        case 1: hipLaunchKernelGGL((KERNEL<3, 1, 1, 1>), __VA_ARGS__); break;                       \
-        case 2: hipLaunchKernelGGL((KERNEL<3, 1, 2, 1>), __VA_ARGS__); break;                       \
-        case 3: hipLaunchKernelGGL((KERNEL<3, 2, 3, 1>), __VA_ARGS__); break;                       \
-        default: hipLaunchKernelGGL((KERNEL<3, 2, 4, 1>), __VA_ARGS__); break;                      \
-      }                                                                                            \
-    }                                                                                              \
-  } while (0)
-
-#define COMMA ,
-// as FLOW5_DISPATCH with trailing template arguments TAIL (write their commas as COMMA)
-#define FLOW5_DISPATCH_T(KERNEL, TAIL, NHd, JB, NP, ...)                                                  \
-  do {                                                                                             \
-    if (NP == 3) {                                                                                 \
-      if (JB == 1) hipLaunchKernelGGL((KERNEL<1, 1, 1, 3, TAIL>), __VA_ARGS__);                           \
-      else hipLaunchKernelGGL((KERNEL<1, 1, 2, 3, TAIL>), __VA_ARGS__);                                   \
-    } else if (NP == 2) {                                                                          \
-      if (JB == 1) hipLaunchKernelGGL((KERNEL<1, 1, 1, 2, TAIL>), __VA_ARGS__);                           \
-      else hipLaunchKernelGGL((KERNEL<1, 1, 2, 2, TAIL>), __VA_ARGS__);                                   \
-    } else if (NHd == 1) {                                                                         \
-      switch (JB) {                                                                                \
-        case 1: hipLaunchKernelGGL((KERNEL<1, 1, 1, 1, TAIL>), __VA_ARGS__); break;                       \
-        case 2: hipLaunchKernelGGL((KERNEL<1, 1, 2, 1, TAIL>), __VA_ARGS__); break;                       \
-        case 3: hipLaunchKernelGGL((KERNEL<1, 2, 3, 1, TAIL>), __VA_ARGS__); break;                       \
-        default: hipLaunchKernelGGL((KERNEL<1, 2, 4, 1, TAIL>), __VA_ARGS__); break;                      \
-      }                                                                                            \
-    } else {                                                                                       \
-      switch (JB) {                                                                                \
-        case 1: hipLaunchKernelGGL((KERNEL<3, 1, 1, 1, TAIL>), __VA_ARGS__); break;                       \
-        case 2: hipLaunchKernelGGL((KERNEL<3, 1, 2, 1, TAIL>), __VA_ARGS__); break;                       \
-        case 3: hipLaunchKernelGGL((KERNEL<3, 2, 3, 1, TAIL>), __VA_ARGS__); break;                       \
-        default: hipLaunchKernelGGL((KERNEL<3, 2, 4, 1, TAIL>), __VA_ARGS__); break;                      \
-      }                                                                                            \
-    }                                                                                              \
-  } while (0)
 
 // the caller supplied the theta branch's factors (VissmFlowParams.theta_rank) and the shape leaves K rows 16..31 of
 // the layer-0 product free
@@ -3111,23 +3040,61 @@ static void launch_prep(const VissmFlowDesc* d, const VissmFlowParams* w, const 
                      d->bn, np_of(d), KB, JB, ws.img, ws.cst, fold ? 1 : 0, lofold ? 1 : 0);
 }
 
-int VISSM_FLOW5_API(flow5_fwd)(const VissmFlowDesc* d, const VissmFlowParams* w, const float* u, const float* C, const int32_t* win,
-              const float* theta_term, float* u_next, float* logsig, void* workspace, size_t ws_bytes,
-              hipStream_t st) {
-  Geom g = geom(d, false);
-  VISSM_CHECK_ARG(workspace && ws_bytes >= ws_layout(d, g, false, nullptr, nullptr), "flow_fwd: workspace too small");
+// what a launch function holds between its prologue and its epilogue
+struct Launch {
+  Geom g;  // set by the caller: geom(d, backward, po)
   Ws ws;
-  ws_layout(d, g, false, reinterpret_cast<char*>(workspace), &ws);
-  const bool f2 = fwd2_ok(d, g), fold = f2 && fold_ok(d, w);
-  const bool lof = f2 && lofold_ok(d);
-  launch_prep(d, w, ws, fold, st, lof);
-  launch_pad(d, w, g, C, theta_term, ws, fold, st);
-  VISSM_CHECK_LAUNCH("flow5_prep");
-  KArgs a = make_args(d, g);
-  const int32_t* wn = d->n_win > 1 ? win : nullptr;
-  dim3 grid((g.n_items + NW - 1) / NW);
-  prof_begin(VISSM_PROF_FLOW_FWD, st);
-  if (f2) {
+  KArgs a;
+};
+
+// Before the kernel: workspace check and layout, the weight fragments (prep_kernel) and the padded inputs.
+// which: 0 forward, 1 backward, 2 the fused last AR flow; what: the entry point's name in the error message
+static int prologue(Launch* L, const VissmFlowDesc* d, const VissmFlowParams* w, const float* C,
+                    const float* theta_term, void* workspace, size_t ws_bytes, int which, bool fold, bool lofold,
+                    const char* what, hipStream_t st) {
+  VISSM_CHECK_ARG(workspace && ws_bytes >= ws_layout(d, L->g, which != 0, nullptr, nullptr, which == 2),
+                  "%s: workspace too small", what);
+  ws_layout(d, L->g, which != 0, reinterpret_cast<char*>(workspace), &L->ws, which == 2);
+  launch_prep(d, w, L->ws, fold, st, lofold);
+  launch_pad(d, w, L->g, C, theta_term, L->ws, fold, st);
+  VISSM_CHECK_LAUNCH(which == 2 ? "flow5_fused_prep" : "flow5_prep");
+  L->a = make_args(d, L->g);
+  return VISSM_OK;
+}
+
+// After a backward kernel (fused or not): the du halo, then the dC, d theta, log sigma (the fused flow's: logsig
+// non-null) and weight-gradient slabs summed in their fixed order, and the scatter into the caller's gradient buffers
+static int bwd_epilogue(const Launch& L, const VissmFlowDesc* d, const VissmFlowParams* w, const int32_t* win,
+                        float* du, float* dC, float* dtheta_term, float* logsig, const VissmFlowGrads* gr,
+                        hipStream_t st) {
+  const Geom& g = L.g;
+  const Ws& ws = L.ws;
+  int rc = du ? launch_halo_fixup(du, ws.halo, d->B, d->L, L.a.pL, d->k, g.n_chunks, g.s, g.CH, st) : VISSM_OK;
+  if (rc) return rc;
+  const int64_t nC = static_cast<int64_t>(g.Lh) * d->H;
+  if (d->n_win == 1) {
+    rc = L.a.dc16 ? launch_reduce_rows_bf16(ws.dC_slab, dC, g.n_groups, nC, st)
+                  : launch_reduce_rows_inplace(ws.dC_slab, dC, g.n_groups, nC, st);
+  } else {
+    rc = launch_reduce_by_window(ws.dC_slab, win, dC, d->B, d->n_win, nC, st);
+  }
+  if (rc) return rc;
+  rc = launch_reduce_rows(ws.dth_slab, dtheta_term, g.n_chunks, static_cast<int64_t>(d->B) * d->H, st);
+  if (rc) return rc;
+  if (logsig) {
+    rc = launch_reduce_rows(ws.zsl, logsig, g.n_chunks, d->B, st);
+    if (rc) return rc;
+  }
+  const int nW = n_wgrad(d);
+  rc = launch_reduce_rows_inplace(ws.dW_slab, ws.wred, g.n_items, nW, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(scatter_wgrad_kernel, dim3((nW + 255) / 256), dim3(256), 0, st, ws.wred, *w, *gr, d->k, d->H,
+                     d->n_hidden, d->bn);
+  VISSM_CHECK_LAUNCH(logsig ? "flow5_fused_scatter" : "flow5_scatter");
+  return VISSM_OK;
+}
+
+
 // 8-wave blocks with every weight plane read from LDS for the split-weight forward (155 -> 93 VGPRs: bf16x2 forward
 // 9.81 -> 9.19 ms per AR-cfg launch) and three hidden layers (225 -> 126: LV 3.68 -> 3.51 ms, FHN 0.77 -> 0.69 ms): the
 // block's weight image then serves twice the waves and the LDS no longer caps them at 2-3 per SIMD; the bf16 AR forward
@@ -3138,129 +3105,115 @@ int VISSM_FLOW5_API(flow5_fwd)(const VissmFlowDesc* d, const VissmFlowParams* w,
                         // the hi planes register-resident, 155 VGPRs: 8.47 -> 9.06 ms per AR-cfg launch,
                         // profiles/r06/ab_r06i.log)
 #endif
-#define FWD2_LAUNCH(TF_, NP_, NH_, JB_, LOF_)                                                                      \
-  do {                                                                                                           \
-    constexpr int nwf = (NP_ == 2 && LOF_) ? VISSM_X2_NWF : (NP_ == 2 || NH_ == 3) ? 8 : NW;                      \
-    hipLaunchKernelGGL((fwd2_kernel<TF_, NP_, NH_, JB_, nwf, LOF_>), dim3((g.n_items + nwf - 1) / nwf),            \
-                       dim3(64 * nwf), 0, st, a, u, ws.Cp, ws.thp, ws.img, ws.cst, u_next, ws.ls_slab, ws.thf);   \
-  } while (0)
-    const int jb = jb_of(d->k);
-    if (d->n_hidden == 3) {
-      if (jb == 1) FWD2_LAUNCH(false, 1, 3, 1, false);
-      else if (jb == 2) FWD2_LAUNCH(false, 1, 3, 2, false);
-      else if (jb == 3) FWD2_LAUNCH(false, 1, 3, 3, false);
-      else FWD2_LAUNCH(false, 1, 3, 4, false);
-    }
-    else if (jb == 2) { if (np_of(d) == 2) FWD2_LAUNCH(false, 2, 1, 2, false); else FWD2_LAUNCH(false, 1, 1, 2, false); }
-    else if (np_of(d) == 2 && lof) { if (fold) FWD2_LAUNCH(true, 2, 1, 1, true); else FWD2_LAUNCH(false, 2, 1, 1, true); }
-    else if (np_of(d) == 2) { if (fold) FWD2_LAUNCH(true, 2, 1, 1, false); else FWD2_LAUNCH(false, 2, 1, 1, false); }
-    else { if (fold) FWD2_LAUNCH(true, 1, 1, 1, false); else FWD2_LAUNCH(false, 1, 1, 1, false); }
-#undef FWD2_LAUNCH
-  } else if (np_of(d) == 2) {
-    if (jb_of(d->k) == 1)
-      hipLaunchKernelGGL((fwd_kernel<1, 1, 1, 2>), grid, dim3(NT), 0, st, a, u, ws.Cp, wn, ws.thp, ws.img, ws.cst, u_next,
-                         ws.ls_slab);
-    else
-      hipLaunchKernelGGL((fwd_kernel<1, 1, 2, 2>), grid, dim3(NT), 0, st, a, u, ws.Cp, wn, ws.thp, ws.img, ws.cst, u_next,
-                         ws.ls_slab);
-  } else {
-    FLOW5_DISPATCH(fwd_kernel, d->n_hidden, jb_of(d->k), np_of(d), grid, dim3(NT), 0, st, a, u, ws.Cp, wn, ws.thp, ws.img,
-                   ws.cst, u_next, ws.ls_slab);
-  }
-  VISSM_CHECK_LAUNCH("flow5_fwd");
-  prof_end(VISSM_PROF_FLOW_FWD, st);
-  return launch_reduce_rows(ws.ls_slab, logsig, g.n_chunks, d->B, st);
+template <bool TF, int NP, int NH, int JB, bool LOF>
+static void launch_fwd2(const Launch& L, const float* u, float* u_next, hipStream_t st) {
+  constexpr int nwf = (NP == 2 && LOF) ? VISSM_X2_NWF : (NP == 2 || NH == 3) ? 8 : NW;
+  hipLaunchKernelGGL((fwd2_kernel<TF, NP, NH, JB, nwf, LOF>), dim3((L.g.n_items + nwf - 1) / nwf), dim3(64 * nwf), 0,
+                     st, L.a, u, L.ws.Cp, L.ws.thp, L.ws.img, L.ws.cst, u_next, L.ws.ls_slab, L.ws.thf);
 }
 
-// whether flow5_bwd runs this descriptor on the bf16 two-sample AR kernel (bwd2_kernel, single-bf16 products):
-// flow_api.hip sends that shape's backward without du to the build of flow_v5f.hip
-bool VISSM_FLOW5_API(flow5_bwd_two_sample_bf16)(const VissmFlowDesc* d) {
+// after a forward kernel: the per-chunk log sigma sums in fixed order
+static int fwd_epilogue(const Launch& L, const VissmFlowDesc* d, float* logsig, hipStream_t st) {
+  VISSM_CHECK_LAUNCH("flow5_fwd");
+  prof_end(VISSM_PROF_FLOW_FWD, st);
+  return launch_reduce_rows(L.ws.ls_slab, logsig, L.g.n_chunks, d->B, st);
+}
+
+
+// gout / dls: the upstream gradients (null in the fused variant, which takes fz instead)
+template <bool FZ, bool DU, bool TF, int NPR, bool SB>
+static void launch_bwd2(const Launch& L, const float* u, const float* gout, const float* dls, float* du,
+                        const FzArgs& fz, hipStream_t st) {
+  hipLaunchKernelGGL((bwd2_kernel<FZ, DU, TF, NPR, SB>), dim3((L.g.n_items + NW2 - 1) / NW2), dim3(NT2), 0, st, L.a, u,
+                     L.ws.Cp, L.ws.thp, gout, dls, L.ws.img, L.ws.cst, du, L.ws.dC_slab, L.ws.dth_slab, L.ws.dW_slab,
+                     L.ws.halo, L.ws.thf, fz);
+}
+
+
+template <int JB, bool S2, bool DU>
+static void launch_bwd2n(const Launch& L, const float* u, const float* du_next, const float* dlogsig, float* du,
+                         hipStream_t st) {
+  hipLaunchKernelGGL((bwd2n_kernel<JB, S2, DU>), dim3((L.g.n_items + NW3 - 1) / NW3), dim3(NT3), 0, st, L.a, u,
+                     L.ws.Cp, L.ws.thp, du_next, dlogsig, L.ws.img, L.ws.cst, du, L.ws.dC_slab, L.ws.dth_slab,
+                     L.ws.dW_slab, L.ws.halo);
+}
+
+}  // namespace VISSM_FLOW5_NS
+}  // namespace vissm
+
+#ifdef VISSM_FLOW5_BASE_UNIT
+// ---------------------------------------------------------------------------
+// the base unit: the descriptor-only functions every unit shares (flow5_supports, workspace size, geometry) and the
+// launch functions of every shape that flow_api.hip sends to no other unit:
+//   * fwd_kernel and bwd_kernel<..., false, DU> in all rows of dispatch_row (several windows, bf16x3, k > 8, ...);
+//   * fwd2_kernel for one hidden layer, and for three hidden layers on one window at 25 <= k <= 32
+//     (fwd2_kernel<false, 1, 3, 2, 8, false>; k <= 24 and k > 32 run from flow_v5n.hip / flow_v5s.hip);
+//   * bwd2_kernel<false, ...> with du, and at bf16x2 without (the bf16 variant without du and the fused last flow run
+//     from flow_v5f.hip).
+// No bwd2n_kernel and no fused variant is compiled here.
+// ---------------------------------------------------------------------------
+namespace vissm {
+namespace flow5 {
+// The unit's kernels, in the order in which they are instantiated.  The order is part of the build: hipcc inlines the
+// shared __forceinline__ helpers (mm, split8, put_image, tr_read, ...) in the order in which they first entered the
+// module, and the one-sample bwd_kernel's instruction stream follows that order (its registers, scratch and LDS do
+// not).  This is the order of the build in which every kernel was measured, when each unit still instantiated all
+// families (scripts/compare_kernel_asm.py against that build: every stream identical,
+// profiles/r08/asm_compare.txt).  Entries marked "order only" are never launched from this unit: they are the
+// fewest kernels of other routes that bring the shared helpers in in that order
+// (profiles/r08/asm_compare_notes.txt).  A kernel added to the unit goes at the end.
+const void* kernel_order(int i) {
+  static const void* const k[] = {
+      (const void*)fwd2_kernel<false, 1, 3, 1, 8, false>,  // order only (flow_v5n / flow_v5s launch it)
+      (const void*)fwd2_kernel<false, 1, 3, 2, 8, false>,
+      (const void*)fwd2_kernel<false, 2, 1, 2, 8, false>, (const void*)fwd2_kernel<false, 1, 1, 2, 4, false>,
+      (const void*)fwd2_kernel<true, 2, 1, 1, 8, true>, (const void*)fwd2_kernel<false, 2, 1, 1, 8, true>,
+      (const void*)fwd2_kernel<true, 2, 1, 1, 8, false>, (const void*)fwd2_kernel<false, 2, 1, 1, 8, false>,
+      (const void*)fwd2_kernel<true, 1, 1, 1, 4, false>, (const void*)fwd2_kernel<false, 1, 1, 1, 4, false>,
+      (const void*)fwd_kernel<1, 1, 1, 2>, (const void*)fwd_kernel<1, 1, 2, 2>,
+      (const void*)fwd_kernel<1, 1, 1, 3>, (const void*)fwd_kernel<1, 1, 2, 3>,
+      (const void*)fwd_kernel<1, 1, 1, 1>, (const void*)fwd_kernel<1, 1, 2, 1>,
+      (const void*)fwd_kernel<1, 2, 3, 1>, (const void*)fwd_kernel<1, 2, 4, 1>,
+      (const void*)fwd_kernel<3, 1, 1, 1>, (const void*)fwd_kernel<3, 1, 2, 1>,
+      (const void*)fwd_kernel<3, 2, 3, 1>, (const void*)fwd_kernel<3, 2, 4, 1>,
+      (const void*)bwd2n_kernel<1, true, true>,  // order only (flow_v5n / flow_v5s launch it)
+      (const void*)bwd2_kernel<false, true, true, 2, true>, (const void*)bwd2_kernel<false, true, false, 2, true>,
+      (const void*)bwd2_kernel<false, false, true, 2, true>, (const void*)bwd2_kernel<false, false, false, 2, true>,
+      (const void*)bwd2_kernel<false, true, true, 1, false>, (const void*)bwd2_kernel<false, true, false, 1, false>,
+      // then bwd_kernel<..., false, true> and bwd_kernel<..., false, false> in dispatch_row's order (flow5_bwd)
+  };
+  return k[i];
+}
+}  // namespace flow5
+using namespace flow5;
+
+bool flow5_supports(const VissmFlowDesc* d) {
+  // one hidden layer (AR): bf16 and bf16x3 (k <= 32: hi + lo images in LDS); three hidden layers
+  // with or without BN (LV / SV / FHN heads): bf16
+  if (d->H > kMaxH || d->k > 64) return false;
+  if (d->precision == VISSM_PREC_BF16) return d->n_hidden == 1 || d->n_hidden == 3;
+  if (d->precision == VISSM_PREC_BF16X3) return d->n_hidden == 1 && d->k <= 32;
+  if (d->precision == VISSM_PREC_BF16X2) return d->n_hidden == 1 && d->k <= 32;
+  return false;
+}
+
+size_t flow5_workspace_size(const VissmFlowDesc* d, int backward) {
+  Geom g = geom(d, backward != 0);
+  return ws_layout(d, g, backward != 0, nullptr, nullptr);
+}
+
+void flow5_geometry(const VissmFlowDesc* d, int which, int32_t* out) {
+  const int po = which == 2 ? P - 1 : P;
+  Geom g = geom(d, which != 0, po);
+  out[0] = po; out[1] = g.CH / po; out[2] = g.n_chunks; out[3] = g.n_groups;
+}
+
+bool flow5_bwd_two_sample_bf16(const VissmFlowDesc* d) {
   const Geom g = geom(d, true);
   return np_of(d) == 1 && !bwd2n_ok(d, g) && bwd2_ok(d, g);
 }
 
-int VISSM_FLOW5_API(flow5_bwd)(const VissmFlowDesc* d, const VissmFlowParams* w, const float* u, const float* C, const int32_t* win,
-              const float* theta_term, const float* du_next, const float* dlogsig, float* du, float* dC,
-              float* dtheta_term, const VissmFlowGrads* gr, void* workspace, size_t ws_bytes, hipStream_t st) {
-  Geom g = geom(d, true);
-  VISSM_CHECK_ARG(workspace && ws_bytes >= ws_layout(d, g, true, nullptr, nullptr), "flow_bwd: workspace too small");
-  Ws ws;
-  ws_layout(d, g, true, reinterpret_cast<char*>(workspace), &ws);
-  const bool b2 = !bwd2n_ok(d, g) && bwd2_ok(d, g), fold = b2 && fold_ok(d, w);
-  launch_prep(d, w, ws, fold, st, b2 && lofold_ok(d));
-  launch_pad(d, w, g, C, theta_term, ws, fold, st);
-  VISSM_CHECK_LAUNCH("flow5_prep");
-  KArgs a = make_args(d, g);
-  const int32_t* wn = d->n_win > 1 ? win : nullptr;
-  dim3 grid(g.blocks);
-  const int pvar = du ? VISSM_PROF_FLOW_BWD_DU : VISSM_PROF_FLOW_BWD_NODU;
-  prof_begin(VISSM_PROF_FLOW_BWD, st);
-  prof_begin(pvar, st);
-  if (bwd2n_ok(d, g)) {
-    const dim3 grid3((g.n_items + NW3 - 1) / NW3);
-#define BWD2N_LAUNCH(JB_, S2_, DU_)                                                                              \
-  hipLaunchKernelGGL((bwd2n_kernel<JB_, S2_, DU_>), grid3, dim3(NT3), 0, st, a, u, ws.Cp, ws.thp, du_next, dlogsig, \
-                     ws.img, ws.cst, du, ws.dC_slab, ws.dth_slab, ws.dW_slab, ws.halo)
-    const int jb = jb_of(d->k);
-    if (d->stride2) {
-      if (jb == 1) { if (du) BWD2N_LAUNCH(1, true, true); else BWD2N_LAUNCH(1, true, false); }
-      else { if (du) BWD2N_LAUNCH(2, true, true); else BWD2N_LAUNCH(2, true, false); }
-    } else {
-      if (jb == 1) { if (du) BWD2N_LAUNCH(1, false, true); else BWD2N_LAUNCH(1, false, false); }
-      else if (jb == 2) { if (du) BWD2N_LAUNCH(2, false, true); else BWD2N_LAUNCH(2, false, false); }
-      else if (jb == 3) { if (du) BWD2N_LAUNCH(3, false, true); else BWD2N_LAUNCH(3, false, false); }
-      else { if (du) BWD2N_LAUNCH(4, false, true); else BWD2N_LAUNCH(4, false, false); }
-    }
-#undef BWD2N_LAUNCH
-  } else if (b2) {
-    const dim3 grid2((g.n_items + NW2 - 1) / NW2);
-#define BWD2_LAUNCH(DU_, TF_, NPR_, SB_)                                                                          \
-  hipLaunchKernelGGL((bwd2_kernel<false, DU_, TF_, NPR_, SB_>), grid2, dim3(NT2), 0, st, a, u, ws.Cp, ws.thp, du_next, \
-                     dlogsig, ws.img, ws.cst, du, ws.dC_slab, ws.dth_slab, ws.dW_slab, ws.halo, ws.thf, FzArgs{})
-    if (np_of(d) == 2) {  // bf16x2: split-weight recompute and backward chain
-      if (du) { if (fold) BWD2_LAUNCH(true, true, 2, true); else BWD2_LAUNCH(true, false, 2, true); }
-      else { if (fold) BWD2_LAUNCH(false, true, 2, true); else BWD2_LAUNCH(false, false, 2, true); }
-    } else {
-      if (du) { if (fold) BWD2_LAUNCH(true, true, 1, false); else BWD2_LAUNCH(true, false, 1, false); }
-      else { if (fold) BWD2_LAUNCH(false, true, 1, false); else BWD2_LAUNCH(false, false, 1, false); }
-    }
-#undef BWD2_LAUNCH
-  } else if (du)
-    FLOW5_DISPATCH_T(bwd_kernel, false COMMA true, d->n_hidden, jb_of(d->k), np_of(d), grid, dim3(NT), 0, st, a, u,
-                     ws.Cp, wn, ws.thp, du_next, dlogsig, ws.img, ws.cst, du, ws.dC_slab, ws.dth_slab, ws.dW_slab,
-                     ws.halo, FzArgs{});
-  else
-    FLOW5_DISPATCH_T(bwd_kernel, false COMMA false, d->n_hidden, jb_of(d->k), np_of(d), grid, dim3(NT), 0, st, a, u,
-                     ws.Cp, wn, ws.thp, du_next, dlogsig, ws.img, ws.cst, du, ws.dC_slab, ws.dth_slab, ws.dW_slab,
-                     ws.halo, FzArgs{});
-  VISSM_CHECK_LAUNCH("flow5_bwd");
-  prof_end(pvar, st);
-  prof_end(VISSM_PROF_FLOW_BWD, st);
-  int rc = du ? launch_halo_fixup(du, ws.halo, d->B, d->L, a.pL, d->k, g.n_chunks, g.s, g.CH, st) : VISSM_OK;
-  if (rc) return rc;
-  const int64_t nC = static_cast<int64_t>(g.Lh) * d->H;
-  if (d->n_win == 1) {
-    rc = a.dc16 ? launch_reduce_rows_bf16(ws.dC_slab, dC, g.n_groups, nC, st)
-                : launch_reduce_rows_inplace(ws.dC_slab, dC, g.n_groups, nC, st);
-    if (rc) return rc;
-  } else {
-    rc = launch_reduce_by_window(ws.dC_slab, win, dC, d->B, d->n_win, nC, st);
-    if (rc) return rc;
-  }
-  rc = launch_reduce_rows(ws.dth_slab, dtheta_term, g.n_chunks, static_cast<int64_t>(d->B) * d->H, st);
-  if (rc) return rc;
-  const int nW = n_wgrad(d);
-  rc = launch_reduce_rows_inplace(ws.dW_slab, ws.wred, g.n_items, nW, st);
-  if (rc) return rc;
-  hipLaunchKernelGGL(VISSM_FLOW5_NS::scatter_wgrad_kernel, dim3((nW + 255) / 256), dim3(256), 0, st, ws.wred, *w, *gr, d->k,
-                     d->H, d->n_hidden, d->bn);
-  VISSM_CHECK_LAUNCH("flow5_scatter");
-  return VISSM_OK;
-}
-
-
-// ---- the last AR(1) flow fused with its ELBO terms (vissm_flow_ar_elbo_fused) ----
-bool VISSM_FLOW5_API(flow5_ar_fused_supports)(const VissmFlowDesc* d) {
+bool flow5_ar_fused_supports(const VissmFlowDesc* d) {
   const bool shape = d->n_hidden == 1 && !d->bn && !d->stride2 && !d->swap_out && d->k <= 32 && d->H <= kMaxH &&
                      d->n_win >= 1;
   if (d->precision == VISSM_PREC_BF16X2 || d->precision == VISSM_PREC_BF16X2_BF16)  // the two-sample kernel's shape only
@@ -3268,91 +3221,127 @@ bool VISSM_FLOW5_API(flow5_ar_fused_supports)(const VissmFlowDesc* d) {
   return (d->precision == VISSM_PREC_BF16 || d->precision == VISSM_PREC_BF16X3) && shape;
 }
 
-size_t VISSM_FLOW5_API(flow5_ar_fused_workspace_size)(const VissmFlowDesc* d) {
+size_t flow5_ar_fused_workspace_size(const VissmFlowDesc* d) {
   Geom g = geom(d, true, P - 1);
   return ws_layout(d, g, true, nullptr, nullptr, true);
 }
 
-#define FLOW5_FZ_DISPATCH(JB, NP, ...)                                                     \
-  do {                                                                                     \
-    if (NP == 3) {                                                                         \
-      if (JB == 1) hipLaunchKernelGGL((bwd_kernel<1, 1, 1, 3, true>), __VA_ARGS__);        \
-      else hipLaunchKernelGGL((bwd_kernel<1, 1, 2, 3, true>), __VA_ARGS__);                \
-    } else {                                                                               \
-      if (JB == 1) hipLaunchKernelGGL((bwd_kernel<1, 1, 1, 1, true>), __VA_ARGS__);        \
-      else hipLaunchKernelGGL((bwd_kernel<1, 1, 2, 1, true>), __VA_ARGS__);                \
-    }                                                                                      \
-  } while (0)
-
-int VISSM_FLOW5_API(flow5_ar_fused)(const VissmFlowDesc* d, const VissmFlowParams* w, const float* u, const float* C, const int32_t* win,
-                   const float* theta_term, const float* theta, const float* obs, const float* obs_bin, float obs_std,
-                   float scale, float* x, float* logsig, float* du, float* dC, float* dtheta_term,
-                   const VissmFlowGrads* gr, void* workspace, size_t ws_bytes, hipStream_t st) {
-  Geom g = geom(d, true, P - 1);
-  VISSM_CHECK_ARG(workspace && ws_bytes >= ws_layout(d, g, true, nullptr, nullptr, true),
-                  "flow_ar_elbo_fused: workspace too small");
-  Ws ws;
-  ws_layout(d, g, true, reinterpret_cast<char*>(workspace), &ws, true);
-  // bf16x2: split-weight recompute and backward chain; bf16x2_bf16: split-weight recompute, bf16 backward products
-  const bool x2 = d->precision == VISSM_PREC_BF16X2 || d->precision == VISSM_PREC_BF16X2_BF16;
-  const bool sb = d->precision == VISSM_PREC_BF16X2;
-  // bf16x2 has only the two-sample kernel: it must meet that kernel's geometry (bwd2_ok minus the precision test)
-  VISSM_CHECK_ARG(!x2 || (g.S == S && d->n_win == 1 && d->k <= KP2),
-                  "flow_ar_elbo_fused: bf16x2 needs the two-sample kernel's geometry (one window, k <= %d)", KP2);
-  const bool b2 = x2 || bwd2_ok(d, g), fold = b2 && fold_ok(d, w);
-  launch_prep(d, w, ws, fold, st, x2 && lofold_ok(d));
-  launch_pad(d, w, g, C, theta_term, ws, fold, st);
-  VISSM_CHECK_LAUNCH("flow5_fused_prep");
-  KArgs a = make_args(d, g);
-  FzArgs fz;
-  fz.theta = theta;
-  fz.obs = obs;
-  fz.bin = obs_bin;
-  fz.x = x;
-  fz.lsl = ws.zsl;
-  fz.scale = scale;
-  fz.iosd = 1.f / obs_std;
-  fz.M = d->L - d->k - 1;
-  const int32_t* wn = d->n_win > 1 ? win : nullptr;
-  prof_begin(VISSM_PROF_FLOW_BWD, st);
-  prof_begin(VISSM_PROF_FLOW_FUSED, st);
-  if (b2) {
-#define BWD2F_LAUNCH(TF_, NPR_, SB_)                                                                                 \
-  hipLaunchKernelGGL((bwd2_kernel<true, true, TF_, NPR_, SB_>), dim3((g.n_items + NW2 - 1) / NW2), dim3(NT2), 0, st, a, u, \
-                     ws.Cp, ws.thp, static_cast<const float*>(nullptr), static_cast<const float*>(nullptr), ws.img,     \
-                     ws.cst, du, ws.dC_slab, ws.dth_slab, ws.dW_slab, ws.halo, ws.thf, fz)
-    if (sb) { if (fold) BWD2F_LAUNCH(true, 2, true); else BWD2F_LAUNCH(false, 2, true); }
-    else if (x2) { if (fold) BWD2F_LAUNCH(true, 2, false); else BWD2F_LAUNCH(false, 2, false); }
-    else { if (fold) BWD2F_LAUNCH(true, 1, false); else BWD2F_LAUNCH(false, 1, false); }
-#undef BWD2F_LAUNCH
-  } else
-    FLOW5_FZ_DISPATCH(jb_of(d->k), np_of(d), dim3(g.blocks), dim3(NT), 0, st, a, u, ws.Cp, wn, ws.thp,
-                      static_cast<const float*>(nullptr), static_cast<const float*>(nullptr), ws.img, ws.cst, du,
-                      ws.dC_slab, ws.dth_slab, ws.dW_slab, ws.halo, fz);
-  VISSM_CHECK_LAUNCH("flow5_fused");
-  prof_end(VISSM_PROF_FLOW_FUSED, st);
-  prof_end(VISSM_PROF_FLOW_BWD, st);
-  int rc = launch_halo_fixup(du, ws.halo, d->B, d->L, a.pL, d->k, g.n_chunks, g.s, g.CH, st);
-  if (rc) return rc;
-  const int64_t nC = static_cast<int64_t>(g.Lh) * d->H;
-  if (d->n_win == 1) {
-    rc = a.dc16 ? launch_reduce_rows_bf16(ws.dC_slab, dC, g.n_groups, nC, st)
-                : launch_reduce_rows_inplace(ws.dC_slab, dC, g.n_groups, nC, st);
+// The one-sample kernels' template row <NH, KB, JB, NP> of a descriptor: f(Row<...>{}) launches it
+template <int NH_, int JB_, int NP_>
+struct Row {
+  static constexpr int NH = NH_, KB = (JB_ + 1) / 2, JB = JB_, NP = NP_;
+};
+template <class F>
+static void dispatch_row(int nh, int jb, int np, F&& f) {
+  if (np == 3) {
+    if (jb == 1) f(Row<1, 1, 3>{});
+    else f(Row<1, 2, 3>{});
+  } else if (np == 2) {
+    if (jb == 1) f(Row<1, 1, 2>{});
+    else f(Row<1, 2, 2>{});
+  } else if (nh == 1) {
+    switch (jb) {
+      case 1: f(Row<1, 1, 1>{}); break;
+      case 2: f(Row<1, 2, 1>{}); break;
+      case 3: f(Row<1, 3, 1>{}); break;
+      default: f(Row<1, 4, 1>{}); break;
+    }
   } else {
-    rc = launch_reduce_by_window(ws.dC_slab, win, dC, d->B, d->n_win, nC, st);
+    switch (jb) {
+      case 1: f(Row<3, 1, 1>{}); break;
+      case 2: f(Row<3, 2, 1>{}); break;
+      case 3: f(Row<3, 3, 1>{}); break;
+      default: f(Row<3, 4, 1>{}); break;
+    }
   }
+}
+
+int flow5_fwd(const VissmFlowDesc* d, const VissmFlowParams* w, const float* u, const float* C, const int32_t* win,
+              const float* theta_term, float* u_next, float* logsig, void* workspace, size_t ws_bytes,
+              hipStream_t st) {
+  Launch L;
+  L.g = geom(d, false);
+  const bool f2 = fwd2_ok(d, L.g), fold = f2 && fold_ok(d, w), lof = f2 && lofold_ok(d);
+  VISSM_CHECK_ARG(!(f2 && d->n_hidden == 3) || (d->k > 24 && d->k <= 32),
+                  "flow_v5: three hidden layers on one window at k=%d run from flow_v5n / flow_v5s", d->k);
+  int rc = prologue(&L, d, w, C, theta_term, workspace, ws_bytes, 0, fold, lof, "flow_fwd", st);
   if (rc) return rc;
-  rc = launch_reduce_rows(ws.dth_slab, dtheta_term, g.n_chunks, static_cast<int64_t>(d->B) * d->H, st);
+  const int jb = jb_of(d->k), np = np_of(d);
+  prof_begin(VISSM_PROF_FLOW_FWD, st);
+  if (f2) {
+    if (d->n_hidden == 3) launch_fwd2<false, 1, 3, 2, false>(L, u, u_next, st);
+    else if (jb == 2) {
+      if (np == 2) launch_fwd2<false, 2, 1, 2, false>(L, u, u_next, st);
+      else launch_fwd2<false, 1, 1, 2, false>(L, u, u_next, st);
+    } else if (np == 2 && lof) {
+      if (fold) launch_fwd2<true, 2, 1, 1, true>(L, u, u_next, st);
+      else launch_fwd2<false, 2, 1, 1, true>(L, u, u_next, st);
+    } else if (np == 2) {
+      if (fold) launch_fwd2<true, 2, 1, 1, false>(L, u, u_next, st);
+      else launch_fwd2<false, 2, 1, 1, false>(L, u, u_next, st);
+    } else {
+      if (fold) launch_fwd2<true, 1, 1, 1, false>(L, u, u_next, st);
+      else launch_fwd2<false, 1, 1, 1, false>(L, u, u_next, st);
+    }
+  } else {
+    const int32_t* wn = d->n_win > 1 ? win : nullptr;
+    dispatch_row(d->n_hidden, jb, np, [&](auto r) {
+      using R = decltype(r);
+      hipLaunchKernelGGL((fwd_kernel<R::NH, R::KB, R::JB, R::NP>), dim3((L.g.n_items + NW - 1) / NW), dim3(NT), 0, st,
+                         L.a, u, L.ws.Cp, wn, L.ws.thp, L.ws.img, L.ws.cst, u_next, L.ws.ls_slab);
+    });
+  }
+  return fwd_epilogue(L, d, logsig, st);
+}
+
+int flow5_bwd(const VissmFlowDesc* d, const VissmFlowParams* w, const float* u, const float* C, const int32_t* win,
+              const float* theta_term, const float* du_next, const float* dlogsig, float* du, float* dC,
+              float* dtheta_term, const VissmFlowGrads* gr, void* workspace, size_t ws_bytes, hipStream_t st) {
+  Launch L;
+  L.g = geom(d, true);
+  VISSM_CHECK_ARG(!bwd2n_ok(d, L.g), "flow_v5: three hidden layers on one window at k=%d run from flow_v5n / flow_v5s",
+                  d->k);
+  const int np = np_of(d);
+  const bool b2 = bwd2_ok(d, L.g), fold = b2 && fold_ok(d, w);
+  VISSM_CHECK_ARG(!b2 || du || np == 2, "flow_v5: the bf16 two-sample backward without du runs from flow_v5f");
+  int rc = prologue(&L, d, w, C, theta_term, workspace, ws_bytes, 1, fold, b2 && lofold_ok(d), "flow_bwd", st);
   if (rc) return rc;
-  rc = launch_reduce_rows(ws.zsl, logsig, g.n_chunks, d->B, st);
-  if (rc) return rc;
-  const int nW = n_wgrad(d);
-  rc = launch_reduce_rows_inplace(ws.dW_slab, ws.wred, g.n_items, nW, st);
-  if (rc) return rc;
-  hipLaunchKernelGGL(VISSM_FLOW5_NS::scatter_wgrad_kernel, dim3((nW + 255) / 256), dim3(256), 0, st, ws.wred, *w, *gr, d->k,
-                     d->H, d->n_hidden, d->bn);
-  VISSM_CHECK_LAUNCH("flow5_fused_scatter");
-  return VISSM_OK;
+  const int pvar = du ? VISSM_PROF_FLOW_BWD_DU : VISSM_PROF_FLOW_BWD_NODU;
+  prof_begin(VISSM_PROF_FLOW_BWD, st);
+  prof_begin(pvar, st);
+  if (b2 && np == 2) {  // bf16x2: split-weight recompute and backward chain
+    if (du) {
+      if (fold) launch_bwd2<false, true, true, 2, true>(L, u, du_next, dlogsig, du, FzArgs{}, st);
+      else launch_bwd2<false, true, false, 2, true>(L, u, du_next, dlogsig, du, FzArgs{}, st);
+    } else {
+      if (fold) launch_bwd2<false, false, true, 2, true>(L, u, du_next, dlogsig, du, FzArgs{}, st);
+      else launch_bwd2<false, false, false, 2, true>(L, u, du_next, dlogsig, du, FzArgs{}, st);
+    }
+  } else if (b2) {
+    if (fold) launch_bwd2<false, true, true, 1, false>(L, u, du_next, dlogsig, du, FzArgs{}, st);
+    else launch_bwd2<false, true, false, 1, false>(L, u, du_next, dlogsig, du, FzArgs{}, st);
+  } else {
+    const int32_t* wn = d->n_win > 1 ? win : nullptr;
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(L.g.blocks), dim3(NT), 0, st, L.a, u, L.ws.Cp, wn, L.ws.thp, du_next, dlogsig,
+                         L.ws.img, L.ws.cst, du, L.ws.dC_slab, L.ws.dth_slab, L.ws.dW_slab, L.ws.halo, FzArgs{});
+    };
+    if (du)
+      dispatch_row(d->n_hidden, jb_of(d->k), np, [&](auto r) {
+        using R = decltype(r);
+        launch(bwd_kernel<R::NH, R::KB, R::JB, R::NP, false, true>);
+      });
+    else
+      dispatch_row(d->n_hidden, jb_of(d->k), np, [&](auto r) {
+        using R = decltype(r);
+        launch(bwd_kernel<R::NH, R::KB, R::JB, R::NP, false, false>);
+      });
+  }
+  VISSM_CHECK_LAUNCH("flow5_bwd");
+  prof_end(pvar, st);
+  prof_end(VISSM_PROF_FLOW_BWD, st);
+  return bwd_epilogue(L, d, w, win, du, dC, dtheta_term, nullptr, gr, st);
 }
 
 }  // namespace vissm
+#endif  // VISSM_FLOW5_BASE_UNIT
