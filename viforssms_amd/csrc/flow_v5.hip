@@ -1400,6 +1400,46 @@ template <bool FZ>
 __device__ __forceinline__ void fence2() {
   if constexpr (FZ) fence();
 }
+// LDS operands read ahead of the MFMAs that use them (bwd2_kernel, NPR = 1; docs/DESIGN_HISTORY.md §11).  Left alone,
+// the compiler reads every weight fragment of a product into one register quad right before its two MFMAs and waits
+// for it with nothing in flight behind it -- s_waitcnt lgkmcnt(0) per fragment, a full LDS latency each time
+// (scripts/lds_wait_profile.py, profiles/r09/lds_waits/).  With the switch on
+//  * each k-step of a weight product (layer 0, hidden layer, head, dX, dcon) reads its fragments as one batch into
+//    registers of their own, and
+//  * each position contraction (dW_head, dW, dW_eps / d theta / dC) issues all its transposed reads before its first
+//    MFMA; dW_head's MFMAs follow the dZ products and elu' multiplies that run while its reads are in flight,
+// and the order "the reads, then the MFMAs" is pinned per phase by sched_group_barrier groups (one sync id per phase:
+// under one id the phases form a single pipeline that the scheduler does not solve), so the waits become counted.
+// No instruction is added or removed and the sequence of MFMAs into every accumulator is the same: results are
+// bitwise those of the switch at 0, which compiles the earlier instruction streams (scripts/compare_kernel_asm.py).
+// VISSM_BWD2_AHEAD_VAR chooses the variants, as measured per AR-cfg launch (profiles/r09/ab_explore.txt,
+// bench_parent_vs_change.txt): 2 the middle flows' du variant (20.36 -> 19.24 ms) and 4 the fused last flow (22.93 ->
+// 21.79 ms) are on; 1 the first flow's variant without du stays off -- its build (flow_v5f.hip: the register-pressure
+// trackers) already schedules most of these reads early (12 of its 47 waits are lgkmcnt(0) against 34 of 56) and
+// the pinned order measured slower there (17.16 -> 17.33 ms).  A masked sched_barrier between the reads and the MFMAs
+// instead of the groups hid as much in the wait model but spilled inside the pair loop of the du variant.
+#ifndef VISSM_BWD2_AHEAD
+#define VISSM_BWD2_AHEAD 1
+#endif
+#ifndef VISSM_BWD2_AHEAD_VAR
+#define VISSM_BWD2_AHEAD_VAR 6
+#endif
+// sched_group_barrier masks
+constexpr int kSgMfma = 0x008, kSgDsRead = 0x100;
+// "N LDS reads, then N groups of M MFMAs" as one pipeline (sync id ID) of the scheduling region; the groups take
+// the nearest such instructions above the call
+template <int ID, int N, int M>
+__device__ __forceinline__ void sg_batch() {
+  __builtin_amdgcn_sched_group_barrier(kSgDsRead, N, ID);
+#pragma unroll
+  for (int i = 0; i < N; ++i) __builtin_amdgcn_sched_group_barrier(kSgMfma, M, ID);
+}
+// "NR LDS reads, then NM MFMAs"
+template <int ID, int NR, int NM>
+__device__ __forceinline__ void sg_seq() {
+  __builtin_amdgcn_sched_group_barrier(kSgDsRead, NR, ID);
+  __builtin_amdgcn_sched_group_barrier(kSgMfma, NM, ID);
+}
 
 // the K = 32 fragment of a position contraction: sample A's transposed fragment then sample B's
 __device__ __forceinline__ bf8 cat8(bf4 a, bf4 b) {
@@ -1428,6 +1468,11 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
   static_assert(!SB || NPR == 2, "the split backward chain goes with the split recompute");
   constexpr int NH = 1, KB = 1, JB = 1, NP = 1;
   constexpr bool LOF = NPR == 2 && !kLoFoldOff;  // the recompute's layer-0 / head lo products in spare rows (k <= 8)
+  // LDS operands read ahead (VISSM_BWD2_AHEAD): the bf16 variants only -- the split-weight ones (NPR = 2) stand at
+  // 254-256 registers with their lo planes' reads between, and the du variant without the theta fold (its theta rows
+  // held beside the C rows) would reload a spilled register inside the pair loop
+  constexpr bool AH =
+      VISSM_BWD2_AHEAD && NPR == 1 && (FZ || TF) && (VISSM_BWD2_AHEAD_VAR & (FZ ? 4 : DU ? 2 : 1)) != 0;
   constexpr int PO = FZ ? P - 1 : P;
   constexpr int QW2 = P + KP2;  // dcon[j][p] stored at column p + j: du[q] = sum_j row_j[q], no masks
   // u window entries: the layer-0 fragment reads up to c + 8 g + 7 <= 46 (48 in the split-weight variants, whose
@@ -1591,19 +1636,30 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
             uf[1].h = tfr[1];
           }
         }
+        if constexpr (AH) {  // the four WE fragments as one batch, then the eight MFMAs
+          bf8 we[4];
 #pragma unroll
-        for (int ob = 0; ob < 4; ++ob) {
-          const Fr8<NP> wf = wfrag(sh, 16 * NH + ob, lane);
-          bf8 wel = {};
-          if constexpr (NPR == 2 && !LOF) {
-            const bf8 v = swe[ob][c];
-            if (g == 0) wel = v;
-          }
+          for (int ob = 0; ob < 4; ++ob) we[ob] = sh.img[16 * NH + ob][0][lane];
 #pragma unroll
-          for (int cb = 0; cb < 2; ++cb) {
-            acc[cb][ob] = X[cb][ob];
-            if constexpr (NPR == 2 && !LOF) acc[cb][ob] = mfma32(wel, uf[cb].h, acc[cb][ob]);
-            acc[cb][ob] = mm<NP>(wf, uf[cb], acc[cb][ob]);
+          for (int ob = 0; ob < 4; ++ob)
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) acc[cb][ob] = mfma32(we[ob], uf[cb].h, X[cb][ob]);
+          sg_batch<1, 4, 2>();
+        } else {
+#pragma unroll
+          for (int ob = 0; ob < 4; ++ob) {
+            const Fr8<NP> wf = wfrag(sh, 16 * NH + ob, lane);
+            bf8 wel = {};
+            if constexpr (NPR == 2 && !LOF) {
+              const bf8 v = swe[ob][c];
+              if (g == 0) wel = v;
+            }
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) {
+              acc[cb][ob] = X[cb][ob];
+              if constexpr (NPR == 2 && !LOF) acc[cb][ob] = mfma32(wel, uf[cb].h, acc[cb][ob]);
+              acc[cb][ob] = mm<NP>(wf, uf[cb], acc[cb][ob]);
+            }
           }
         }
 #pragma unroll
@@ -1631,13 +1687,25 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
           Fr8<NP> xf[2] = {chain_frag<NP>(X[0], ks), chain_frag<NP>(X[1], ks)};
+          if constexpr (AH) {  // the k-step's four WF fragments as one batch
+            bf8 wq[4];
 #pragma unroll
-          for (int ob = 0; ob < 4; ++ob) {
-            const Fr8<NP> wf = wfrag(sh, ob * 2 + ks, lane);
+            for (int ob = 0; ob < 4; ++ob) wq[ob] = sh.img[ob * 2 + ks][0][lane];
 #pragma unroll
-            for (int cb = 0; cb < 2; ++cb) {
-              if constexpr (NPR == 2) acc[cb][ob] = mfma32(slo[ob * 2 + ks][lane], xf[cb].h, acc[cb][ob]);
-              acc[cb][ob] = mm<NP>(wf, xf[cb], acc[cb][ob]);
+            for (int ob = 0; ob < 4; ++ob)
+#pragma unroll
+              for (int cb = 0; cb < 2; ++cb) acc[cb][ob] = mfma32(wq[ob], xf[cb].h, acc[cb][ob]);
+            if (ks == 0) sg_batch<2, 4, 2>();
+            else sg_batch<3, 4, 2>();
+          } else {
+#pragma unroll
+            for (int ob = 0; ob < 4; ++ob) {
+              const Fr8<NP> wf = wfrag(sh, ob * 2 + ks, lane);
+#pragma unroll
+              for (int cb = 0; cb < 2; ++cb) {
+                if constexpr (NPR == 2) acc[cb][ob] = mfma32(slo[ob * 2 + ks][lane], xf[cb].h, acc[cb][ob]);
+                acc[cb][ob] = mm<NP>(wf, xf[cb], acc[cb][ob]);
+              }
             }
           }
         }
@@ -1670,14 +1738,23 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb)
           if (g == 3) X[cb][3][3] = 1.f;
+        if constexpr (AH) {  // both WH fragments, then the four MFMAs
+          const bf8 wh[2] = {sh.img[fh][0][lane], sh.img[fh + 1][0][lane]};
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          const Fr8<NP> wf = wfrag(sh, fh + ks, lane);
+          for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-          for (int cb = 0; cb < 2; ++cb) {
-            const Fr8<NP> xk = chain_frag<NP>(X[cb], ks);
-            if constexpr (NPR == 2 && !LOF) d[cb] = mfma32(slo[8 + ks][lane], xk.h, d[cb]);
-            d[cb] = mm<NP>(wf, xk, d[cb]);
+            for (int cb = 0; cb < 2; ++cb) d[cb] = mfma32(wh[ks], chain_frag<NP>(X[cb], ks).h, d[cb]);
+          sg_batch<4, 2, 2>();
+        } else {
+#pragma unroll
+          for (int ks = 0; ks < 2; ++ks) {
+            const Fr8<NP> wf = wfrag(sh, fh + ks, lane);
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) {
+              const Fr8<NP> xk = chain_frag<NP>(X[cb], ks);
+              if constexpr (NPR == 2 && !LOF) d[cb] = mfma32(slo[8 + ks][lane], xk.h, d[cb]);
+              d[cb] = mm<NP>(wf, xk, d[cb]);
+            }
           }
         }
 #pragma unroll
@@ -1787,10 +1864,13 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
       fence2<FZ || (!DU && VISSM_NODU_FENCES)>();
       // dW_head[h][o] += sum over both samples' positions of I_1[h][p] G[o][p] (K = 32): block 3 of the same
       // fragments is the B operand (its columns 5, 6 are the G rows)
-      {
-        bf8 i1f[4];
+      // (read ahead: the I_1 fragments are only ISSUED here -- before the dZ image's put_image into the same slot
+      // below, which is all that a wave's in-order LDS needs -- and their MFMAs follow that store, so that the dZ
+      // products and the elu' multiplies run while the reads are in flight)
+      bf8 i1f[4];
 #pragma unroll
-        for (int hb = 0; hb < 4; ++hb) i1f[hb] = tr_frag2(im1, hb, g, c);
+      for (int hb = 0; hb < 4; ++hb) i1f[hb] = tr_frag2(im1, hb, g, c);
+      if constexpr (!AH) {
 #pragma unroll
         for (int hb = 0; hb < 4; ++hb) dWh[hb] = mfma32(i1f[hb], i1f[3], dWh[hb]);
       }
@@ -1828,6 +1908,11 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
           put_image<NP>(im1 + cb * P * HP, nullptr, D[cb], g, c);
         }
       }
+      if constexpr (AH) {
+#pragma unroll
+        for (int hb = 0; hb < 4; ++hb) dWh[hb] = mfma32(i1f[hb], i1f[3], dWh[hb]);
+        sg_seq<8, 8, 4>();
+      }
       fence2<FZ || (!DU && VISSM_NODU_FENCES)>();
       // dX = W~ dZ (chain), both samples
       f4 dX[2][4];
@@ -1838,13 +1923,25 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
         Fr8<NP> df[2] = {chain_frag<NP>(D[0], ks), chain_frag<NP>(D[1], ks)};
+        if constexpr (AH) {  // the k-step's four WB fragments as one batch
+          bf8 wq[4];
 #pragma unroll
-        for (int ib = 0; ib < 4; ++ib) {
-          const Fr8<NP> wb = wfrag(sh, 8 * NH + ib * 2 + ks, lane);
+          for (int ib = 0; ib < 4; ++ib) wq[ib] = sh.img[8 * NH + ib * 2 + ks][0][lane];
 #pragma unroll
-          for (int cb = 0; cb < 2; ++cb) {
-            if constexpr (SB) dX[cb][ib] = mfma32(slo[RO + ib * 2 + ks][lane], df[cb].h, dX[cb][ib]);
-            dX[cb][ib] = mm<NP>(wb, df[cb], dX[cb][ib]);
+          for (int ib = 0; ib < 4; ++ib)
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) dX[cb][ib] = mfma32(wq[ib], df[cb].h, dX[cb][ib]);
+          if (ks == 0) sg_batch<5, 4, 2>();
+          else sg_batch<6, 4, 2>();
+        } else {
+#pragma unroll
+          for (int ib = 0; ib < 4; ++ib) {
+            const Fr8<NP> wb = wfrag(sh, 8 * NH + ib * 2 + ks, lane);
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) {
+              if constexpr (SB) dX[cb][ib] = mfma32(slo[RO + ib * 2 + ks][lane], df[cb].h, dX[cb][ib]);
+              dX[cb][ib] = mm<NP>(wb, df[cb], dX[cb][ib]);
+            }
           }
         }
       }
@@ -1854,11 +1951,22 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
         bf8 dzf[4];
 #pragma unroll
         for (int ob = 0; ob < 4; ++ob) dzf[ob] = tr_frag2(im1, ob, g, c);
+        if constexpr (AH) {  // all sixteen reads (dZ from slot 1 before the dA0 image goes there), then the MFMAs
+          bf8 xa[4];
 #pragma unroll
-        for (int ib = 0; ib < 4; ++ib) {
-          const bf8 xa = tr_frag2(im0, ib, g, c);
+          for (int ib = 0; ib < 4; ++ib) xa[ib] = tr_frag2(im0, ib, g, c);
 #pragma unroll
-          for (int ob = 0; ob < 4; ++ob) dW[ib][ob] = mfma32(xa, dzf[ob], dW[ib][ob]);
+          for (int ib = 0; ib < 4; ++ib)
+#pragma unroll
+            for (int ob = 0; ob < 4; ++ob) dW[ib][ob] = mfma32(xa[ib], dzf[ob], dW[ib][ob]);
+          sg_seq<9, 16, 16>();
+        } else {
+#pragma unroll
+          for (int ib = 0; ib < 4; ++ib) {
+            const bf8 xa = tr_frag2(im0, ib, g, c);
+#pragma unroll
+            for (int ob = 0; ob < 4; ++ob) dW[ib][ob] = mfma32(xa, dzf[ob], dW[ib][ob]);
+          }
         }
       }
       // dA0 = dX * elu'(I_0) (I_0 from the registers the forward left: the image's bf16 values)
@@ -1878,7 +1986,14 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
         }
       // dcon[j][p] = sum_h w_eps[j][h] dA0[h][p] per sample; the dC tile += dA0 of both
       f4 dcn[2] = {f4{0.f, 0.f, 0.f, 0.f}, f4{0.f, 0.f, 0.f, 0.f}};
-      if constexpr (DU) {
+      if constexpr (DU && AH) {  // both WC fragments, then the four MFMAs
+        const bf8 wc[2] = {sh.img[fwc][0][lane], sh.img[fwc + 1][0][lane]};
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+          for (int cb = 0; cb < 2; ++cb) dcn[cb] = mfma32(wc[ks], chain_frag<NP>(D[cb], ks).h, dcn[cb]);
+        sg_batch<7, 2, 2>();
+      } else if constexpr (DU) {
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
           const Fr8<NP> wc = wfrag(sh, fwc + ks, lane);
@@ -1927,11 +2042,23 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
           const unsigned ta_ = c - 8 == (blv[0] & 7) ? one2 : 0u, tb_ = (two && c - 8 == (blv[1] & 7)) ? one2 : 0u;
           if (c >= 8) bcomb = __builtin_bit_cast(bf8, u4{ta_, ta_, tb_, tb_});
         }
+        if constexpr (AH) {  // the dA0 image's eight reads, then the eight MFMAs
+          bf8 ta[4];
 #pragma unroll
-        for (int hb = 0; hb < 4; ++hb) {
-          const bf8 ta = tr_frag2(im1, hb, g, c);
-          dWe[hb] = mfma32(ta, bcomb, dWe[hb]);
-          dCa[hb] = mfma32(ta, sel_p, dCa[hb]);
+          for (int hb = 0; hb < 4; ++hb) ta[hb] = tr_frag2(im1, hb, g, c);
+#pragma unroll
+          for (int hb = 0; hb < 4; ++hb) {
+            dWe[hb] = mfma32(ta[hb], bcomb, dWe[hb]);
+            dCa[hb] = mfma32(ta[hb], sel_p, dCa[hb]);
+          }
+          sg_seq<10, 8, 8>();
+        } else {
+#pragma unroll
+          for (int hb = 0; hb < 4; ++hb) {
+            const bf8 ta = tr_frag2(im1, hb, g, c);
+            dWe[hb] = mfma32(ta, bcomb, dWe[hb]);
+            dCa[hb] = mfma32(ta, sel_p, dCa[hb]);
+          }
         }
       }
       // the eight sample columns flushed into the per-sample d theta rows after every fourth pair and after the
