@@ -1418,11 +1418,34 @@ __device__ __forceinline__ void fence2() {
 // trackers) already schedules most of these reads early (12 of its 47 waits are lgkmcnt(0) against 34 of 56) and
 // the pinned order measured slower there (17.16 -> 17.33 ms).  A masked sched_barrier between the reads and the MFMAs
 // instead of the groups hid as much in the wait model but spilled inside the pair loop of the du variant.
+// Level 2 (docs/DESIGN_HISTORY.md §12) takes what level 1 left in the wait tables: LDS latencies paid one operation
+// at a time at the pair loop's tail and, in the fused variant's build, in batches that level 1's groups did not hold
+// together.  One mask of sites per variant (VISSM_BWD2_TAIL_DU / _FZ / _NODU); a site is on where its launch measured
+// faster and the pair loop stayed free of scratch (profiles/r10/ab_explore.txt):
+//    1  the du section's eight dcon rows read as one batch above the dW_eps / d theta / dC contraction   (du, fused)
+//    2  with them g_mu, sigma and the carry slot (du variant: spills into the pair loop)                 (fused)
+//    4  the dW_eps operand's u-window reads above the elu' multiplies                                    (du, no-du)
+//    8  layer 0's four weight fragments held in flight together by a sched_barrier behind the reads: in the fused
+//       variant's build (the register-pressure trackers) the scheduler folded level 1's batch back into one register
+//       quad, three of the four reads waited for alone                                                   (fused)
+//   16  the same for both k-steps of dX                                                                  (fused)
+//   32  the head phase's u[c + k] read ahead of the head MFMAs instead of inside the softplus block      (fused)
+// Level 1 compiles the instruction streams of before level 2, level 0 those of before level 1.  No site changes a
+// float operation or its order: outputs are bitwise those of level 1 (profiles/r10/dump_compare.txt).
 #ifndef VISSM_BWD2_AHEAD
-#define VISSM_BWD2_AHEAD 1
+#define VISSM_BWD2_AHEAD 2
 #endif
 #ifndef VISSM_BWD2_AHEAD_VAR
 #define VISSM_BWD2_AHEAD_VAR 6
+#endif
+#ifndef VISSM_BWD2_TAIL_DU
+#define VISSM_BWD2_TAIL_DU 5
+#endif
+#ifndef VISSM_BWD2_TAIL_FZ
+#define VISSM_BWD2_TAIL_FZ 59
+#endif
+#ifndef VISSM_BWD2_TAIL_NODU
+#define VISSM_BWD2_TAIL_NODU 4
 #endif
 // sched_group_barrier masks
 constexpr int kSgMfma = 0x008, kSgDsRead = 0x100;
@@ -1473,6 +1496,10 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
   // held beside the C rows) would reload a spilled register inside the pair loop
   constexpr bool AH =
       VISSM_BWD2_AHEAD && NPR == 1 && (FZ || TF) && (VISSM_BWD2_AHEAD_VAR & (FZ ? 4 : DU ? 2 : 1)) != 0;
+  // the sites of level 2 (above): the bf16 variants with the theta fold (the fused variant without it, its theta rows
+  // held beside the C rows, would reload a spilled register inside the pair loop with them)
+  constexpr int TAIL = (VISSM_BWD2_AHEAD >= 2 && NPR == 1 && TF)
+                           ? (FZ ? VISSM_BWD2_TAIL_FZ : DU ? VISSM_BWD2_TAIL_DU : VISSM_BWD2_TAIL_NODU) : 0;
   constexpr int PO = FZ ? P - 1 : P;
   constexpr int QW2 = P + KP2;  // dcon[j][p] stored at column p + j: du[q] = sum_j row_j[q], no masks
   // u window entries: the layer-0 fragment reads up to c + 8 g + 7 <= 46 (48 in the split-weight variants, whose
@@ -1625,6 +1652,7 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
       u2 i0p[2][4];
       u2 d0p[2][4], d1p[2][4];  // VISSM_DERIV16: elu'(A0), elu'(A1) as f16 pairs
       float mu[2], rr[2];
+      float uk_e = 0.f;
       {
         f4 acc[2][4];
         fence2<FZ || (!DU && VISSM_NODU_FENCES)>();
@@ -1640,11 +1668,12 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
           bf8 we[4];
 #pragma unroll
           for (int ob = 0; ob < 4; ++ob) we[ob] = sh.img[16 * NH + ob][0][lane];
+          if constexpr ((TAIL & 8) != 0) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
           for (int ob = 0; ob < 4; ++ob)
 #pragma unroll
             for (int cb = 0; cb < 2; ++cb) acc[cb][ob] = mfma32(we[ob], uf[cb].h, X[cb][ob]);
-          sg_batch<1, 4, 2>();
+          if constexpr ((TAIL & 8) == 0) sg_batch<1, 4, 2>();
         } else {
 #pragma unroll
           for (int ob = 0; ob < 4; ++ob) {
@@ -1738,6 +1767,7 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb)
           if (g == 3) X[cb][3][3] = 1.f;
+        if constexpr (FZ && (TAIL & 32) != 0) uk_e = uwin[w][g >> 1][c + a.k];
         if constexpr (AH) {  // both WH fragments, then the four MFMAs
           const bf8 wh[2] = {sh.img[fh][0][lane], sh.img[fh + 1][0][lane]};
 #pragma unroll
@@ -1780,7 +1810,7 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
         const bool hv = hs == 0 || two;             // not the ghost
         const float mu_h = hs ? mu[1] : mu[0], rr_h = hs ? rr[1] : rr[0];
         const float sig_h = softplus_fast(rr_h) + 1e-10f;
-        const float uk = uwin[w][hs][c + a.k];
+        const float uk = (TAIL & 32) ? uk_e : uwin[w][hs][c + a.k];
         const float x = uk * sig_h + mu_h;
         float xp = row_prev(x);
         const float xn = row_next(x);
@@ -1927,11 +1957,13 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
           bf8 wq[4];
 #pragma unroll
           for (int ib = 0; ib < 4; ++ib) wq[ib] = sh.img[8 * NH + ib * 2 + ks][0][lane];
+          if constexpr ((TAIL & 16) != 0) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
           for (int ib = 0; ib < 4; ++ib)
 #pragma unroll
             for (int cb = 0; cb < 2; ++cb) dX[cb][ib] = mfma32(wq[ib], df[cb].h, dX[cb][ib]);
-          if (ks == 0) sg_batch<5, 4, 2>();
+          if constexpr ((TAIL & 16) != 0) {
+          } else if (ks == 0) sg_batch<5, 4, 2>();
           else sg_batch<6, 4, 2>();
         } else {
 #pragma unroll
@@ -1968,6 +2000,14 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
             for (int ob = 0; ob < 4; ++ob) dW[ib][ob] = mfma32(xa, dzf[ob], dW[ib][ob]);
           }
         }
+      }
+      // the dW_eps operand's u-window reads ahead (TAIL & 4): the windows stand in LDS since the unit's inputs and are
+      // next written by the next pair's inputs, so the reads may go anywhere in between; issued here, their latency
+      // passes under the elu' multiplies instead of in front of the packing that feeds the dW_eps MFMAs
+      bf8 uaf_e = {};
+      if constexpr ((TAIL & 4) != 0) {
+        const Fr4<NP> ua = ua_frag<NP>(uwin[w][0], 1, 0, g, c), ub = ua_frag<NP>(uwin[w][1], 1, 0, g, c);
+        uaf_e = cat8(ua.h, ub.h);
       }
       // dA0 = dX * elu'(I_0) (I_0 from the registers the forward left: the image's bf16 values)
 #pragma unroll
@@ -2026,12 +2066,39 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
             for (int r = 0; r < 4; ++r) dscr[w][cb][4 * g + r][c + 4 * g + r] = dcn[cb][r];
         }
       }
+      // The du section's LDS inputs read ahead (TAIL & 1, 2): the eight dcon rows -- and with TAIL & 2 g_mu, sigma and
+      // the carry slot -- are read here as one batch, and the section (below the dW_eps / d theta / dC MFMAs) only
+      // sums them, so that the latencies it paid one by one pass under that contraction.  A wave's LDS operations execute
+      // in order, so
+      //  * the dscr reads see this pair's dcon stores (just above) and none of the next pair's (after its dcon MFMAs);
+      //  * gwin and gsc were written in this pair's head backward and are next written in the next pair's inputs
+      //    (gwin) and head backward (gsc), both behind these reads;
+      //  * the carry slot [sample][q < k] was last written by the previous tile's pair of the same two samples, an
+      //    earlier iteration; this pair's carry write (q >= nP, the du section) stays behind this read of the same
+      //    slot and ahead of the next tile's read of it, which is a later iteration of the tile loop.
+      // The reads are unmasked (clamped indices; lanes outside the section's range discard them).
+      float dut[KP2], dug = 0.f, dus = 0.f, duc = 0.f;
+      const auto du_rows = [&]() {
+        const int cbq = lane >> 5, q = lane & 31;
+        const int qc = q < QW2 ? q : QW2 - 1;
+#pragma unroll
+        for (int j = 0; j < KP2; ++j) dut[j] = dscr[w][cbq][j][qc];
+      };
+      const auto du_terms = [&]() {
+        const int cbq = lane >> 5, q = lane & 31;
+        const int oqc = min(max(q - a.k, 0), P - 1);
+        dug = gwin[w][cbq][oqc];
+        dus = gsc[w][cbq][oqc];
+        duc = carry[w][cbq ? blv[1] : blv[0]][q & (KP2 - 1)];
+      };
+      if constexpr (DU && (TAIL & 1) != 0) du_rows();
+      if constexpr (DU && (TAIL & 2) != 0) du_terms();
       fence2<FZ || (!DU && VISSM_NODU_FENCES)>();
       // dW_eps and d theta from dA0's position-contracted fragments (K = 32)
       {
         const unsigned one2 = 0x3F803F80u;
-        bf8 uaf;
-        {
+        bf8 uaf = uaf_e;
+        if constexpr ((TAIL & 4) == 0) {
           const Fr4<NP> ua = ua_frag<NP>(uwin[w][0], 1, 0, g, c), ub = ua_frag<NP>(uwin[w][1], 1, 0, g, c);
           uaf = cat8(ua.h, ub.h);
         }
@@ -2095,15 +2162,21 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
           const int qc = q < QW2 ? q : QW2 - 1;
           float t[KP2];
 #pragma unroll
-          for (int j = 0; j < KP2; ++j) t[j] = dscr[w][cbq][j][qc];
+          for (int j = 0; j < KP2; ++j) t[j] = (TAIL & 1) ? dut[j] : dscr[w][cbq][j][qc];
 #pragma unroll
           for (int w2 = 1; w2 < KP2; w2 *= 2)
 #pragma unroll
             for (int j = 0; j + w2 < KP2; j += 2 * w2) t[j] += t[j + w2];
           v = t[0];
           const int oq2 = q - a.k;
-          if (oq2 >= 0 && oq2 < nP) v += NPR == 2 ? gwin[w][cbq][oq2] : gwin[w][cbq][oq2] * gsc[w][cbq][oq2];
-          if (q < a.k) v += carry[w][blq][q];
+          if constexpr ((TAIL & 2) != 0) {
+            if (oq2 >= 0 && oq2 < nP) v += dug * dus;
+            if (q < a.k) v += duc;
+          } else {
+            if (oq2 >= 0 && oq2 < nP)
+              v += NPR == 2 ? gwin[w][cbq][oq2] : gwin[w][cbq][oq2] * gsc[w][cbq][oq2];
+            if (q < a.k) v += carry[w][blq][q];
+          }
         }
         // (16-byte du stores of full aligned tiles -- four lanes' values gathered by DPP row shifts -- measured 0.2 ms
         // slower per middle-flow launch and no fewer PMC write bytes (4.05 vs 4.07 GB), profiles/r05/ab_step.log)
