@@ -499,6 +499,62 @@ int vissm_theta_branch_bwd(int32_t B, int32_t P, int32_t n0, int32_t n1, int32_t
                            float* dW2, float* db2, void* workspace, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Column statistics of a sample-major matrix: posterior summaries computed where
+ * the samples are.  They replace the reference's host path from posterior samples
+ * to credible bands -- VI_SSM.save_paths writes every sample of every window with
+ * np.savetxt (AR.py:323-362) and vis.py takes the quantiles of that file offline.
+ *
+ * x is [B][pitch] fp32, columns 0..n_cols-1 used, pitch >= n_cols; the base pointer
+ * needs only the 4-byte alignment of its elements (x[:, 1:]-style views).
+ *
+ * Moments: sums[0][c] = sum of x[b][c], sums[1][c] = sum of squares, both over the
+ * non-NaN entries in double, n_valid[c] their count.  Per-row-slab partials in the
+ * workspace, then a fixed-order sum: bitwise reproducible, no float atomics.
+ *
+ * Order statistics: an exact 4-pass byte-wise radix select on the order key
+ *   -0 -> +0; any NaN -> 0xFFFFFFFF; else, with b the float's bits,
+ *   key = (b >> 31) ? ~b : (b | 0x80000000)
+ * whose unsigned order is numpy's sort order (-inf .. +inf, NaN last).  Each column
+ * has n_ranks targets (1..16), target r asking for the element of 0-based rank
+ * rank_left[c][r] of the sorted column.  Pass p = 0..3 looks at key byte 3 - p:
+ *   hist:   hist[c][r][256] = counts of that byte over the elements of column c
+ *           whose key bytes above it equal those of prefix[c][r] (pass 0: every
+ *           element; prefix is read but its value ignored).  Overwrites hist.
+ *           Integer counts: independent of the order of the adds, so the ranks of
+ *           a data-parallel run SUM-all-reduce hist here and select over the
+ *           union of their samples exactly, without gathering them.
+ *   narrow: per (c, r) the digit d with cum[d-1] <= rank_left < cum[d] of the
+ *           histogram it is given; rank_left -= cum[d-1]; prefix |= d << shift
+ *           (pass 0 starts from prefix 0).  A rank outside [0, total count) is
+ *           clamped to the nearest valid one.
+ *   decode: out[r][c] = the float of key prefix[c][r] (0xFFFFFFFF: a quiet NaN).
+ * The global sample count (all ranks' B) must stay below 2^31.  Workspace sizes:
+ * host arithmetic only, 0 = bad descriptor; they depend on the number of row slabs
+ * (at most 256), not on B * n_cols.
+ * ------------------------------------------------------------------------- */
+typedef struct {
+  int32_t B, n_cols, pitch; /* rows, used columns, row pitch (elements) */
+  int32_t n_ranks;          /* order-statistic targets per column, 1..16 (the moments ignore it beyond the range) */
+} VissmColStatDesc;
+
+/* replaces: the mean / sd of the host np.savetxt -> offline summary path (AR.py:323-362, vis.py) */
+size_t vissm_col_moments_workspace_size(const VissmColStatDesc* d);
+int vissm_col_moments(const VissmColStatDesc* d, const float* x, double* sums /* [2][n_cols] */,
+                      int32_t* n_valid /* [n_cols] */, void* workspace, void* stream);
+/* the four below replace: the host np.savetxt -> offline quantile path (AR.py:323-362, vis.py) */
+/* scratch of the select (AR.py:323-362 / vis.py keep every sample on the host instead) */
+size_t vissm_col_select_workspace_size(const VissmColStatDesc* d);
+/* one byte's histograms: the counting half of vis.py's column-wise quantile over the save_paths file */
+int vissm_col_select_hist(const VissmColStatDesc* d, const float* x, const uint32_t* prefix /* [n_cols][n_ranks] */,
+                          int32_t pass, int32_t* hist /* [n_cols][n_ranks][256] */, void* workspace, void* stream);
+/* the digit that holds each rank: the selecting half of the same quantile (AR.py:323-362, vis.py) */
+int vissm_col_select_narrow(const VissmColStatDesc* d, const int32_t* hist, int32_t* rank_left /* in/out */,
+                            uint32_t* prefix /* in/out */, int32_t pass, void* stream);
+/* keys back to floats: the order statistics vis.py reads off the sorted file (AR.py:323-362) */
+int vissm_col_select_decode(const VissmColStatDesc* d, const uint32_t* prefix, float* out /* [n_ranks][n_cols] */,
+                            void* stream);
+
+/* ---------------------------------------------------------------------------
  * Opt-in kernel timing (for bench.py's live roofline): when enabled, the flow
  * entry points bracket their main kernel with hipEvents on the launch stream.
  * kind: VISSM_PROF_FLOW_FWD / VISSM_PROF_FLOW_BWD (flow kernels),

@@ -45,10 +45,13 @@ def run(argv=None):
     data_gen(hp.T, hp.impute, hp.x0, np.array(hp.theta), hp.obs_std, write=(ctx.rank == 0))
     barrier(ctx)
     prec = TRAIN_PRECISIONS[args.precision]
-    return ar.main(hp.p, hp.kernel_len, hp.T, hp.batch_dims, hp.network_dims, hp.no_flows, hp.priors,
-                   hp.feat_window, hp.x0, hp.obs_std, learn_rate=hp.learn_rate, grad_clip=hp.grad_clip,
-                   max_runs=args.steps, precision=prec, dist=ctx, seed=args.seed, pre_train=not args.no_pretrain,
-                   log_every=args.log_every, graph=args.graph)
+    model = ar.main(hp.p, hp.kernel_len, hp.T, hp.batch_dims, hp.network_dims, hp.no_flows, hp.priors,
+                    hp.feat_window, hp.x0, hp.obs_std, learn_rate=hp.learn_rate, grad_clip=hp.grad_clip,
+                    max_runs=args.steps, precision=prec, dist=ctx, seed=args.seed, pre_train=not args.no_pretrain,
+                    log_every=args.log_every, graph=args.graph)
+    if args.summary:
+        model.save_summary(args.summary)   # every rank: its collectives span the ranks; rank 0 writes
+    return model
 
 
 if __name__ == "__main__":

@@ -101,6 +101,13 @@ class ElboData(ctypes.Structure):
                                         "obs_list")] + [("obs_stride", ctypes.c_int32)]
 
 
+COLSTAT_MAX_RANKS = 16
+
+
+class ColStatDesc(ctypes.Structure):
+    _fields_ = [(n, _i32) for n in ("B", "n_cols", "pitch", "n_ranks")]
+
+
 # exported symbol -> (restype, argtypes); tests check that every symbol of include/vissm.h is here
 SIGNATURES = {
     "vissm_last_error": (ctypes.c_char_p, []),
@@ -170,6 +177,14 @@ SIGNATURES = {
     "vissm_theta_branch_bwd": (_i32, [_i32] * 5 + [_c_void_p] * 15 + [_size_t, _c_void_p]),
     "vissm_theta_bwd": (_i32, [ctypes.POINTER(ThetaDesc), _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                                _c_void_p, _c_void_p, _size_t, _c_void_p]),
+    "vissm_col_moments_workspace_size": (_size_t, [ctypes.POINTER(ColStatDesc)]),
+    "vissm_col_moments": (_i32, [ctypes.POINTER(ColStatDesc), _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "vissm_col_select_workspace_size": (_size_t, [ctypes.POINTER(ColStatDesc)]),
+    "vissm_col_select_hist": (_i32, [ctypes.POINTER(ColStatDesc), _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p,
+                                     _c_void_p]),
+    "vissm_col_select_narrow": (_i32, [ctypes.POINTER(ColStatDesc), _c_void_p, _c_void_p, _c_void_p, _i32,
+                                       _c_void_p]),
+    "vissm_col_select_decode": (_i32, [ctypes.POINTER(ColStatDesc), _c_void_p, _c_void_p, _c_void_p]),
     "vissm_profile_enable": (None, [_i32]),
     "vissm_profile_read": (_i32, [_i32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_i64)]),
     "vissm_profile_reset": (None, []),

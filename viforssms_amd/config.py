@@ -129,6 +129,9 @@ def handle_opts(argv=None):
     parser.add_argument("--log-every", type=int, default=1)
     parser.add_argument("--graph", action="store_true",
                         help="Run the ELBO steps as a captured HIP graph (launch-bound small configs)")
+    parser.add_argument("--summary", metavar="PATH", default=None,
+                        help="After training, write the posterior summary (mean, sd and quantile bands of the latent "
+                             "path over time and of theta, computed on the GPU) to this .npz file")
     return parser.parse_args(argv)
 
 

@@ -5,6 +5,7 @@
 
 #include "../../include/vissm.h"
 #include "elbo_math.hpp"
+#include "colstat_math.hpp"
 
 extern "C" {
 
@@ -28,14 +29,23 @@ float vissm_host_sp_ildj(float y, float* gy) { return vissm::em::sp_ildj(y, gy);
 
 float vissm_host_obs(float x, float y, float bin, float sd, float* gx) { return vissm::em::obs_term(x, y, bin, sd, gx); }
 
+// the column statistics' order key, its inverse and one narrowing step of the radix select (colstat_math.hpp: the
+// code the kernels of colstat.hip run); hist is one (column, target)'s 256 bins
+uint32_t vissm_host_colkey(float x) { return vissm::cs::colkey(x); }
+float vissm_host_colkey_inv(uint32_t key) { return vissm::cs::colkey_inv(key); }
+void vissm_host_col_narrow(const int32_t* hist, int32_t* rank_left, uint32_t* prefix, int pass) {
+  vissm::cs::col_narrow(hist, rank_left, prefix, pass);
+}
+
 // the C ABI's struct layouts as the C compiler sees them (the ctypes mirrors in viforssms_amd/_lib.py are
-// checked against these): which = 0 VissmFlowDesc, 1 VissmFlowParams, 2 VissmFlowGrads, 3 VissmElboData; out = {size,
+// checked against these): which = 0 VissmFlowDesc, 1 VissmFlowParams, 2 VissmFlowGrads, 3 VissmElboData, 4 VissmColStatDesc; out = {size,
 // offset of the last field}
 void vissm_host_abi_layout(int which, size_t* out) {
   switch (which) {
     case 0: out[0] = sizeof(VissmFlowDesc); out[1] = offsetof(VissmFlowDesc, out_pitch); break;
     case 1: out[0] = sizeof(VissmFlowParams); out[1] = offsetof(VissmFlowParams, theta_rank); break;
     case 2: out[0] = sizeof(VissmFlowGrads); out[1] = offsetof(VissmFlowGrads, b_head); break;
+    case 4: out[0] = sizeof(VissmColStatDesc); out[1] = offsetof(VissmColStatDesc, n_ranks); break;
     default: out[0] = sizeof(VissmElboData); out[1] = offsetof(VissmElboData, obs_stride); break;
   }
 }

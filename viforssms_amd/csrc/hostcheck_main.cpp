@@ -3,19 +3,27 @@
 // (tests/test_lib.py::test_hostcheck_sanitized).  Each model's hand-derived transition
 // gradient is checked against central finite differences of its own log-density over
 // a fixed pseudo-random grid of states and parameters, and the ABI layout query is
-// exercised; any sanitizer report aborts the run (-fno-sanitize-recover=all).
+// exercised; the column statistics' order key, its inverse and the radix select's narrowing
+// step (colstat_math.hpp) are checked against the floats' own order and std::nth_element;
+// any sanitizer report aborts the run (-fno-sanitize-recover=all).
 // Exit 0 = all checks passed.  Not part of the product path.
 #include <cmath>
 #include <cstddef>
 #include <cstdio>
 #include <cstdint>
+#include <cstring>
+#include <algorithm>
 #include <initializer_list>
+#include <vector>
 
 extern "C" {
 void vissm_host_trans(int model, const float* xh, const float* xt, const float* th, float dt, float* out);
 float vissm_host_sp_ildj(float y, float* gy);
 float vissm_host_obs(float x, float y, float bin, float sd, float* gx);
 void vissm_host_abi_layout(int which, size_t* out);
+uint32_t vissm_host_colkey(float x);
+float vissm_host_colkey_inv(uint32_t key);
+void vissm_host_col_narrow(const int32_t* hist, int32_t* rank_left, uint32_t* prefix, int pass);
 }
 
 namespace {
@@ -93,6 +101,87 @@ int check_model(int model, int cases) {
   return bad;
 }
 
+float from_bits(uint32_t b) {
+  float x;
+  std::memcpy(&x, &b, sizeof x);
+  return x;
+}
+
+uint32_t to_bits(float x) {
+  uint32_t b;
+  std::memcpy(&b, &x, sizeof b);
+  return b;
+}
+
+// key order == the floats' order with NaN last, and inverse(key(x)) == x (-0 -> +0, NaN -> NaN), over +-0,
+// +-denormals, +-inf, NaNs of both signs and 10^4 random bit patterns
+int check_colkey() {
+  std::vector<float> v;
+  for (uint32_t b : {0x00000000u, 0x80000000u, 0x00000001u, 0x80000001u, 0x007FFFFFu, 0x807FFFFFu, 0x00800000u,
+                     0x80800000u, 0x7F7FFFFFu, 0xFF7FFFFFu, 0x7F800000u, 0xFF800000u, 0x7FC00000u, 0xFFC00000u,
+                     0x7F800001u, 0xFFFFFFFFu, 0x3F800000u, 0xBF800000u})
+    v.push_back(from_bits(b));
+  for (int i = 0; i < 10000; ++i) v.push_back(from_bits(static_cast<uint32_t>(uniform(0.0, 4294967296.0))));
+  int bad = 0;
+  for (size_t i = 0; i < v.size(); ++i) {
+    const float x = v[i];
+    const uint32_t k = vissm_host_colkey(x);
+    const float back = vissm_host_colkey_inv(k);
+    if (std::isnan(x)) {
+      if (k != 0xFFFFFFFFu || !std::isnan(back)) { std::printf("colkey: NaN %08x -> %08x\n", to_bits(x), k); ++bad; }
+      continue;
+    }
+    if (k == 0xFFFFFFFFu) { std::printf("colkey: %g got the NaN key\n", x); ++bad; }
+    const uint32_t want = x == 0.f ? 0u : to_bits(x);
+    if (to_bits(back) != want) { std::printf("colkey: %08x -> %08x -> %08x\n", to_bits(x), k, to_bits(back)); ++bad; }
+  }
+  for (size_t i = 0; i < v.size(); ++i)
+    for (size_t j = i + 1; j < std::min(v.size(), i + 40); ++j) {
+      const float a = v[i], b = v[j];
+      const uint32_t ka = vissm_host_colkey(a), kb = vissm_host_colkey(b);
+      const bool na = std::isnan(a), nb = std::isnan(b);
+      const bool ok = na || nb ? (ka < kb) == (!na && nb) && (kb < ka) == (!nb && na)
+                               : (ka < kb) == (a < b) && (kb < ka) == (b < a);
+      if (!ok) { std::printf("colkey order: %g (%08x) vs %g (%08x)\n", a, ka, b, kb); ++bad; }
+    }
+  return bad;
+}
+
+// the 4-pass select on a host array (histogram of one key byte over the elements matching the prefix, then narrow)
+// equals std::nth_element at every rank of a 300-element array with ties
+int check_select() {
+  std::vector<float> x(300);
+  for (size_t i = 0; i < x.size(); ++i) {
+    const int kind = static_cast<int>(uniform(0.0, 4.0));
+    x[i] = kind == 0   ? static_cast<float>(static_cast<int>(uniform(-3.0, 4.0)))
+           : kind == 1 ? static_cast<float>(uniform(-1e3, 1e3))
+           : kind == 2 ? 1.f + static_cast<float>(static_cast<int>(uniform(0.0, 20.0))) * 0x1.0p-23f
+                       : static_cast<float>(uniform(-1e-3, 1e-3));
+  }
+  x[7] = 0.f; x[8] = -0.f; x[9] = INFINITY; x[10] = -INFINITY; x[11] = from_bits(1u); x[12] = from_bits(0x80000001u);
+  int bad = 0;
+  for (int rank = 0; rank < static_cast<int>(x.size()); ++rank) {
+    int32_t left = rank;
+    uint32_t prefix = 0;
+    for (int pass = 0; pass < 4; ++pass) {
+      int32_t hist[256] = {0};
+      const int shift = 8 * (3 - pass);
+      for (float v : x) {
+        const uint32_t k = vissm_host_colkey(v);
+        if (pass == 0 || (k >> (shift + 8)) == (prefix >> (shift + 8))) ++hist[(k >> shift) & 255u];
+      }
+      vissm_host_col_narrow(hist, &left, &prefix, pass);
+    }
+    std::vector<float> y(x);
+    std::nth_element(y.begin(), y.begin() + rank, y.end());
+    const float got = vissm_host_colkey_inv(prefix);
+    // +0 and -0 compare equal and either may sit at the rank: the select returns +0
+    // (what is left of the rank counts the ties below it, never negative)
+    if (!(got == y[rank]) || left < 0) { std::printf("select rank %d: %g vs %g (left %d)\n", rank, got, y[rank], left); ++bad; }
+  }
+  return bad;
+}
+
 }  // namespace
 
 int main() {
@@ -112,7 +201,9 @@ int main() {
   float gx = 0.f;
   const float o = vissm_host_obs(1.5f, 1.0f, 1.f, 0.5f, &gx);
   if (!std::isfinite(o) || std::fabs(gx + 2.f) > 1e-5f) { std::printf("obs_term: gx %g\n", gx); ++bad; }
-  for (int which = 0; which < 3; ++which) {
+  bad += check_colkey();
+  bad += check_select();
+  for (int which = 0; which < 5; ++which) {
     size_t out[2] = {0, 0};
     vissm_host_abi_layout(which, out);
     if (out[0] == 0 || out[1] >= out[0]) { std::printf("abi layout %d: %zu %zu\n", which, out[0], out[1]); ++bad; }

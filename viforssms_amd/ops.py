@@ -843,3 +843,80 @@ class ThetaFlowFn(torch.autograd.Function):
                                   ptr(ctx.grad_slice), ptr(ws), ws.numel(), _lib.stream_handle(x0.device)),
               "vissm_theta_bwd")
         return None, None, None, None, None, None
+
+
+# ---------------------------------------------------------------------------------------
+# column statistics (posterior summaries)
+# ---------------------------------------------------------------------------------------
+def _colstat_desc(x: torch.Tensor, n_ranks: int = 1) -> "_lib.ColStatDesc":
+    """Descriptor of a [B, n_cols] fp32 GPU matrix with unit inner stride; the rows may lie any pitch >= n_cols
+    apart and the view may start anywhere in its storage (x[:, 1:]): the kernels assume 4-byte alignment only."""
+    if x.dim() != 2 or not x.is_cuda or x.dtype != torch.float32:
+        raise _lib.VissmError("column statistics: a 2-D fp32 GPU tensor is expected (there is deliberately no CPU "
+                              "fallback)")
+    B, n = x.shape
+    if B < 1 or n < 1:
+        raise _lib.VissmError(f"column statistics: empty input {tuple(x.shape)}")
+    if n > 1 and x.stride(1) != 1:
+        raise _lib.VissmError("column statistics: unit inner stride expected")
+    pitch = x.stride(0) if B > 1 else n
+    if pitch < n:
+        raise _lib.VissmError(f"column statistics: row stride {pitch} below the {n} columns")
+    return _lib.ColStatDesc(B, n, pitch, n_ranks)
+
+
+def col_moments(x: torch.Tensor):
+    """(sums [2, n_cols] float64: sum and sum of squares over the non-NaN entries of each column, n_valid [n_cols]
+    int32) of x [B, n_cols] (vissm_col_moments: fixed-order double accumulation, bitwise reproducible)."""
+    lib = _lib.load()
+    d = _colstat_desc(x)
+    dev = x.device
+    sums = torch.empty(2, d.n_cols, dtype=torch.float64, device=dev)
+    n_valid = torch.empty(d.n_cols, dtype=torch.int32, device=dev)
+    ws = _workspace(lib.vissm_col_moments_workspace_size(ctypes.byref(d)), dev)
+    check(lib.vissm_col_moments(ctypes.byref(d), ptr(x), ptr(sums), ptr(n_valid), ptr(ws), _lib.stream_handle(dev)),
+          "vissm_col_moments")
+    return sums, n_valid
+
+
+def col_order_stats(x: torch.Tensor, ranks: torch.Tensor, dist=None) -> torch.Tensor:
+    """Exact order statistics of the columns of x [B, n_cols]: out[r, c] = the element of 0-based rank ranks[c, r]
+    of column c sorted as numpy sorts it (-inf .. +inf, NaN last), [n_ranks, n_cols] fp32.  ranks: int tensor
+    [n_cols, n_ranks], or [n_ranks] for every column, at most 16 per column.  Four passes of
+    vissm_col_select_hist -> (SUM all-reduce over `dist`, a vi_ssm.DistCtx, when its world > 1: the ranks then index
+    the union of all processes' rows) -> vissm_col_select_narrow, then vissm_col_select_decode.  Ranks given on the
+    host are checked against [0, rows of all processes); ranks on the device are not read back (no host
+    synchronisation here) and the narrowing step clamps them to that range."""
+    lib = _lib.load()
+    world = dist.world if dist is not None else 1
+    if not isinstance(ranks, torch.Tensor) or ranks.dtype not in (torch.int32, torch.int64) or ranks.dim() not in (1, 2):
+        raise _lib.VissmError("col_order_stats: ranks must be an int tensor [n_cols, n_ranks] or [n_ranks]")
+    n_ranks = ranks.shape[-1]
+    if not 1 <= n_ranks <= _lib.COLSTAT_MAX_RANKS:
+        raise _lib.VissmError(f"col_order_stats: {n_ranks} ranks per column (1..{_lib.COLSTAT_MAX_RANKS})")
+    d = _colstat_desc(x, n_ranks)
+    total = d.B * world
+    if total >= 2 ** 31:
+        raise _lib.VissmError(f"col_order_stats: {total} rows over all processes (must stay below 2^31)")
+    if ranks.dim() == 2 and ranks.shape[0] != d.n_cols:
+        raise _lib.VissmError(f"col_order_stats: ranks {tuple(ranks.shape)} for {d.n_cols} columns")
+    if not ranks.is_cuda and ranks.numel() and (int(ranks.min()) < 0 or int(ranks.max()) >= total):
+        raise _lib.VissmError(f"col_order_stats: ranks outside [0, {total})")
+    dev = x.device
+    rank_left = ranks.to(device=dev, dtype=torch.int32).expand(d.n_cols, n_ranks).contiguous()
+    if rank_left.data_ptr() == ranks.data_ptr():
+        rank_left = rank_left.clone()   # narrowed in place
+    prefix = torch.empty(d.n_cols, n_ranks, dtype=torch.int32, device=dev)   # uint32 keys
+    hist = torch.empty(d.n_cols, n_ranks, 256, dtype=torch.int32, device=dev)
+    ws = _workspace(lib.vissm_col_select_workspace_size(ctypes.byref(d)), dev)
+    st = _lib.stream_handle(dev)
+    for p in range(4):
+        check(lib.vissm_col_select_hist(ctypes.byref(d), ptr(x), ptr(prefix), p, ptr(hist), ptr(ws), st),
+              "vissm_col_select_hist")
+        if world > 1:
+            dist.all_reduce_(hist)
+        check(lib.vissm_col_select_narrow(ctypes.byref(d), ptr(hist), ptr(rank_left), ptr(prefix), p, st),
+              "vissm_col_select_narrow")
+    out = torch.empty(n_ranks, d.n_cols, dtype=torch.float32, device=dev)
+    check(lib.vissm_col_select_decode(ctypes.byref(d), ptr(prefix), ptr(out), st), "vissm_col_select_decode")
+    return out

@@ -18,6 +18,7 @@ import torch
 
 from . import _lib
 from .nma import Engine, ModelDef, Batch, AdamaxSlots, ScalarLog
+from .summary import DEFAULT_PROBS, column_summary
 
 
 @dataclass
@@ -561,3 +562,51 @@ class VISSMBase:
             os.makedirs(d, exist_ok=True)
         with open(PATH_obs, "w") as f:
             np.savetxt(f, np.reshape(paths, (paths.shape[0], -1)) if paths.shape[1] > 1 else paths[:, 0, :])
+
+    # ------------------------------------------------------------------ posterior summaries
+    @torch.no_grad()
+    def sample_paths_theta(self, starts: np.ndarray, step: int = 0):
+        """sample_paths with the draw's theta next to the paths: (x [B, D, M+1], theta [B, P])."""
+        batch = self.engine.make_batch(np.asarray(starts))
+        out = self.forward(batch, step)
+        return self.engine.lf_sample(out["z"], batch), out["theta"]
+
+    @torch.no_grad()
+    def posterior_summary(self, probs=DEFAULT_PROBS) -> Dict[str, np.ndarray]:
+        """Mean, sd and quantile bands of the latent path over time and of theta, over exactly the samples save_paths
+        would write (the same window starts, draws and step) and, with several ranks, over all of them -- computed on
+        the GPU (summary.column_summary), so only the summaries reach the host instead of every sample of every
+        window (AR.py:323-362 and the offline quantiles of vis.py).  paths/{mean, sd} are [D, T], paths/quantiles
+        [Q, D, T]; theta/{mean, sd} [P], theta/quantiles [Q, P] come from the first window's draw, log-parameters
+        exponentiated as in histograms().  Every rank takes part in the collectives and gets the same result."""
+        M = self.batch_dims
+        parts = []
+        res: Dict[str, np.ndarray] = {"probs": np.asarray(list(probs), dtype=np.float64)}
+        for idx in np.arange(0, self.target_len(), M):
+            x, theta = self.sample_paths_theta(np.tile(idx, self.p_local), step=self.global_step)
+            xs = x[:, :, 1:]
+            B, D, m = xs.shape
+            x2 = xs[:, 0, :] if D == 1 else xs.reshape(B, D * m)   # a pitched, offset view / a contiguous copy
+            parts.append((D, m, column_summary(x2.float(), probs, self.dist)))
+            if "theta/mean" not in res:
+                th = theta.detach().float()
+                pos = list(self.mdef.theta_pos)
+                if any(pos):
+                    th = torch.where(torch.tensor(pos, device=th.device), th.exp(), th)
+                for k, v in column_summary(th.contiguous(), probs, self.dist).items():
+                    res[f"theta/{k}"] = v
+        for k in ("mean", "sd", "n_valid"):
+            res[f"paths/{k}"] = np.concatenate([s[k].reshape(D, m) for D, m, s in parts], axis=1)
+        res["paths/quantiles"] = np.concatenate([s["quantiles"].reshape(-1, D, m) for D, m, s in parts], axis=2)
+        return res
+
+    def save_summary(self, PATH: str, probs=DEFAULT_PROBS) -> Dict[str, np.ndarray]:
+        """posterior_summary written as one .npz by rank 0 (every rank computes it: the collectives need them all)."""
+        res = self.posterior_summary(probs)
+        if self.dist.rank == 0:
+            d = os.path.dirname(PATH)
+            if d:
+                os.makedirs(d, exist_ok=True)
+            with open(PATH, "wb") as f:
+                np.savez(f, **res)
+        return res
