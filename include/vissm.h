@@ -212,6 +212,9 @@ int vissm_flow_ar_elbo_fused(const VissmFlowDesc* d, const VissmFlowParams* w,
 #define VISSM_MODEL_LV 1
 #define VISSM_MODEL_SV 2
 #define VISSM_MODEL_FHN 3
+/* state coordinates S and theta length P of a model id */
+#define VISSM_MODEL_S(model) ((model) == VISSM_MODEL_AR ? 1 : 2)
+#define VISSM_MODEL_P(model) ((model) == VISSM_MODEL_SV ? 4 : (model) == VISSM_MODEL_FHN ? 5 : 3)
 
 typedef struct {
   int32_t model;
@@ -553,6 +556,47 @@ int vissm_col_select_narrow(const VissmColStatDesc* d, const int32_t* hist, int3
 /* keys back to floats: the order statistics vis.py reads off the sorted file (AR.py:323-362) */
 int vissm_col_select_decode(const VissmColStatDesc* d, const uint32_t* prefix, float* out /* [n_ranks][n_cols] */,
                             void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Forward simulation of the four SDEs by Euler-Maruyama, one sample per lane: posterior-predictive forecasts
+ * from the fitted model's per-sample theta and last latent state.  The reference has no forecast; its only forward
+ * simulations are the host data generators (AR_dat_gen.py:6-43 and the one-path numpy loops that restate the
+ * transition models of lotka_volterra_partial.py:244-261, SV_dense.py:203-223, fitz_nag_NVP.py:243-255), one path in
+ * float64.  The step is the transition vissm_elbo_fwd scores (csrc/sim_math.hpp, theta raw: logs where the density
+ * exponentiates them):
+ *   AR  : x' = th1 x + th0 + e^th2 n0
+ *   LV  : x' = x + dt (e0 x1 - Bv, Bv - e2 x2) + sqrt(dt) chol([[A, -Bv], [-Bv, Cc]]) n,
+ *         e_i = e^th_i, Bv = e1 x1 x2, A = e0 x1 + Bv, Cc = Bv + e2 x2
+ *   SV  : x1' = x1 + dt th0 x1 + sqrt(dt) x1 e^{x2/2} n0;  x2' = x2 + dt (th1 - e^th2 x2) + sqrt(dt) e^th3 n1
+ *   FHN : x' = x + dt (e^th0 (x1 - x1^3 - x2 + th1), th2 x1 - x2 + 1.4) + sqrt(dt) (sqrt(e^th3) n0, sqrt(e^th4) n1)
+ * with S = VISSM_MODEL_S(model) state coordinates and P = VISSM_MODEL_P(model) parameters.  A sample whose new
+ * state is not finite -- for LV also one with a coordinate <= 0 -- is dead: that step and every later one of its
+ * row are NaN in x, y and x_end (the column statistics leave NaN out and count n_valid).  A start state that fails
+ * the same test gives a NaN row.
+ *
+ * Randomness: drawn in the kernel, the stream of vissm_normal_base.  Sample b at absolute step t0 + t uses entries
+ * j = (t0 + t) n_stream + i of Philox row row0 + b under key seed (counter (j / 4, 0, row)), i < S the state
+ * normals, then with observations S more: y[b][d][t] = x[b][d][t] + obs_std n_{S + d}.  n_stream = S without
+ * observations, 2 S with them (not SV, whose first coordinate is the observed series).  So
+ * vissm_normal_base(seed, row0, .., B, n_stream H_total, ..) returns the numbers consumed, whatever the launch
+ * geometry, the sharding of B over ranks or the cut of the horizon into calls: t0 > 0 with x_start = the previous
+ * call's x_end continues a simulation bitwise ((t0 + H) n_stream must stay below 2^31).
+ *
+ * x, y: [B][S][H] sample-major (what vissm_col_* summarise); x_end [B][S] the state after the last step (x_start
+ * for H = 0).  Each wave stages VISSM_SIM_TILE steps of its 64 samples in LDS and writes them out row by row,
+ * 64 lanes on consecutive steps of one sample.  No workspace, no atomics: bitwise reproducible.
+ * ------------------------------------------------------------------------- */
+#define VISSM_SIM_TILE 64
+typedef struct {
+  int32_t model, B, H, t0, n_stream;
+  float dt, obs_std;
+  int32_t with_obs;
+} VissmSimDesc;
+
+int vissm_sde_simulate(const VissmSimDesc* d, uint64_t seed, uint64_t row0,
+                       const float* theta /* [B][P] */, const float* x_start /* [B][S] */,
+                       float* x /* [B][S][H] */, float* y /* [B][S][H] or NULL */,
+                       float* x_end /* [B][S] */, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Opt-in kernel timing (for bench.py's live roofline): when enabled, the flow

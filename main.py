@@ -51,6 +51,8 @@ def run(argv=None):
                     log_every=args.log_every, graph=args.graph)
     if args.summary:
         model.save_summary(args.summary)   # every rank: its collectives span the ranks; rank 0 writes
+    if args.forecast:
+        model.save_forecast(args.forecast[1], args.forecast[0])   # every rank, as the summary
     return model
 
 

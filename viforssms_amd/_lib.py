@@ -30,6 +30,9 @@ TRAIN_PRECISIONS = {"fp32": VISSM_PREC_FP32, "bf16": VISSM_PREC_BF16, "bf16x3": 
                     "bf16x2": VISSM_PREC_BF16X2, "bf16x3f": VISSM_PREC_BF16X3F, "bf16x2f": VISSM_PREC_BF16X2F}
 
 MODEL_AR, MODEL_LV, MODEL_SV, MODEL_FHN = 0, 1, 2, 3
+MODEL_S = {MODEL_AR: 1, MODEL_LV: 2, MODEL_SV: 2, MODEL_FHN: 2}   # VISSM_MODEL_S: state coordinates
+MODEL_P = {MODEL_AR: 3, MODEL_LV: 3, MODEL_SV: 4, MODEL_FHN: 5}   # VISSM_MODEL_P: theta length
+SIM_TILE = 64   # VISSM_SIM_TILE: steps a wave of vissm_sde_simulate stages in LDS before it writes them out
 
 _c_void_p = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -106,6 +109,11 @@ COLSTAT_MAX_RANKS = 16
 
 class ColStatDesc(ctypes.Structure):
     _fields_ = [(n, _i32) for n in ("B", "n_cols", "pitch", "n_ranks")]
+
+
+class SimDesc(ctypes.Structure):
+    _fields_ = ([(n, _i32) for n in ("model", "B", "H", "t0", "n_stream")] + [("dt", _f32), ("obs_std", _f32)] +
+                [("with_obs", _i32)])
 
 
 # exported symbol -> (restype, argtypes); tests check that every symbol of include/vissm.h is here
@@ -185,6 +193,8 @@ SIGNATURES = {
     "vissm_col_select_narrow": (_i32, [ctypes.POINTER(ColStatDesc), _c_void_p, _c_void_p, _c_void_p, _i32,
                                        _c_void_p]),
     "vissm_col_select_decode": (_i32, [ctypes.POINTER(ColStatDesc), _c_void_p, _c_void_p, _c_void_p]),
+    "vissm_sde_simulate": (_i32, [ctypes.POINTER(SimDesc), _u64, _u64, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                  _c_void_p, _c_void_p]),
     "vissm_profile_enable": (None, [_i32]),
     "vissm_profile_read": (_i32, [_i32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_i64)]),
     "vissm_profile_reset": (None, []),

@@ -132,7 +132,18 @@ def handle_opts(argv=None):
     parser.add_argument("--summary", metavar="PATH", default=None,
                         help="After training, write the posterior summary (mean, sd and quantile bands of the latent "
                              "path over time and of theta, computed on the GPU) to this .npz file")
-    return parser.parse_args(argv)
+    parser.add_argument("--forecast", nargs=2, metavar=("H", "PATH"), default=None,
+                        help="After training, simulate the fitted model H steps past the data on the GPU and write the "
+                             "posterior-predictive forecast (mean, sd and quantile bands over time) to this .npz file")
+    args = parser.parse_args(argv)
+    if args.forecast is not None:
+        try:
+            args.forecast = (int(args.forecast[0]), args.forecast[1])
+        except ValueError:
+            parser.error(f"--forecast: the horizon must be an integer, got {args.forecast[0]!r}")
+        if args.forecast[0] < 0:
+            parser.error("--forecast: the horizon must not be negative")
+    return args
 
 
 def apply_overrides(hp: HyperParams, args) -> HyperParams:

@@ -1,11 +1,13 @@
 // Host (CPU) build of elbo_math.hpp so the CPU test-suite can check the
-// hand-derived transition gradients against the oracle's autograd without a GPU.
+// hand-derived transition gradients against the oracle's autograd without a GPU,
+// and of sim_math.hpp (the forecast kernel's Euler-Maruyama steps) against a float64 restatement.
 // Not part of the product path: libvissm_hostcheck.so is loaded only by tests/.
 #include <cstddef>
 
 #include "../../include/vissm.h"
 #include "elbo_math.hpp"
 #include "colstat_math.hpp"
+#include "sim_math.hpp"
 
 extern "C" {
 
@@ -37,14 +39,30 @@ void vissm_host_col_narrow(const int32_t* hist, int32_t* rank_left, uint32_t* pr
   vissm::cs::col_narrow(hist, rank_left, prefix, pass);
 }
 
+// One Euler-Maruyama step of sim_math.hpp (the code simulate.hip runs): out[0 .. S) = the next state from x, raw
+// theta, dt and standard normals n[0 .. S), without the death rule
+void hc_sim_step(int model, const float* x, const float* th, float dt, const float* n, float* out) {
+  vissm::sim::step_rt(model, x, th, dt, n, out);
+}
+
+// H steps from given normals [H][n_stream] (n_stream = S, or 2 S when y_out is not null), with the death rule:
+// x_out / y_out [S][H], x_end [S]
+void hc_sim_path(int model, const float* x_start, const float* th, float dt, float obs_std, int H,
+                 const float* normals, float* x_out, float* y_out, float* x_end) {
+  vissm::sim::path_rt(model, x_start, th, dt, obs_std, H, normals, x_out, y_out, x_end);
+}
+
+int hc_sim_alive(int model, const float* x) { return vissm::sim::alive(model, x) ? 1 : 0; }
+
 // the C ABI's struct layouts as the C compiler sees them (the ctypes mirrors in viforssms_amd/_lib.py are
-// checked against these): which = 0 VissmFlowDesc, 1 VissmFlowParams, 2 VissmFlowGrads, 3 VissmElboData, 4 VissmColStatDesc; out = {size,
+// checked against these): which = 0 VissmFlowDesc, 1 VissmFlowParams, 2 VissmFlowGrads, 3 VissmElboData, 4 VissmColStatDesc, 5 VissmSimDesc; out = {size,
 // offset of the last field}
 void vissm_host_abi_layout(int which, size_t* out) {
   switch (which) {
     case 0: out[0] = sizeof(VissmFlowDesc); out[1] = offsetof(VissmFlowDesc, out_pitch); break;
     case 1: out[0] = sizeof(VissmFlowParams); out[1] = offsetof(VissmFlowParams, theta_rank); break;
     case 2: out[0] = sizeof(VissmFlowGrads); out[1] = offsetof(VissmFlowGrads, b_head); break;
+    case 5: out[0] = sizeof(VissmSimDesc); out[1] = offsetof(VissmSimDesc, with_obs); break;
     case 4: out[0] = sizeof(VissmColStatDesc); out[1] = offsetof(VissmColStatDesc, n_ranks); break;
     default: out[0] = sizeof(VissmElboData); out[1] = offsetof(VissmElboData, obs_stride); break;
   }

@@ -5,6 +5,8 @@
 // a fixed pseudo-random grid of states and parameters, and the ABI layout query is
 // exercised; the column statistics' order key, its inverse and the radix select's narrowing
 // step (colstat_math.hpp) are checked against the floats' own order and std::nth_element;
+// the forecast's Euler-Maruyama steps (sim_math.hpp) are run for each model against a double restatement, over a
+// dying LV row and over H = 0 and 1;
 // any sanitizer report aborts the run (-fno-sanitize-recover=all).
 // Exit 0 = all checks passed.  Not part of the product path.
 #include <cmath>
@@ -24,6 +26,9 @@ void vissm_host_abi_layout(int which, size_t* out);
 uint32_t vissm_host_colkey(float x);
 float vissm_host_colkey_inv(uint32_t key);
 void vissm_host_col_narrow(const int32_t* hist, int32_t* rank_left, uint32_t* prefix, int pass);
+void hc_sim_step(int model, const float* x, const float* th, float dt, const float* n, float* out);
+void hc_sim_path(int model, const float* x_start, const float* th, float dt, float obs_std, int H,
+                 const float* normals, float* x_out, float* y_out, float* x_end);
 }
 
 namespace {
@@ -182,6 +187,111 @@ int check_select() {
   return bad;
 }
 
+// one step of each model in double, from the formulas of sim_math.hpp's header comment
+void sim_step_ref(int model, const float* xf, const float* thf, double dt, const float* nf, double* out) {
+  double x[2] = {xf[0], xf[1]}, th[5], n[2] = {nf[0], nf[1]};
+  for (int i = 0; i < 5; ++i) th[i] = thf[i];
+  const double sq = std::sqrt(dt);
+  if (model == 0) {
+    out[0] = th[1] * x[0] + th[0] + std::exp(th[2]) * n[0];
+  } else if (model == 1) {
+    const double e0 = std::exp(th[0]), e1 = std::exp(th[1]), e2 = std::exp(th[2]);
+    const double Bv = e1 * x[0] * x[1], A = e0 * x[0] + Bv, Cc = Bv + e2 * x[1];
+    const double a = std::sqrt(A), b = -Bv / a, c = std::sqrt(Cc - b * b);
+    out[0] = x[0] + dt * (e0 * x[0] - Bv) + sq * a * n[0];
+    out[1] = x[1] + dt * (Bv - e2 * x[1]) + sq * (b * n[0] + c * n[1]);
+  } else if (model == 2) {
+    out[0] = x[0] + dt * th[0] * x[0] + sq * x[0] * std::exp(0.5 * x[1]) * n[0];
+    out[1] = x[1] + dt * (th[1] - std::exp(th[2]) * x[1]) + sq * std::exp(th[3]) * n[1];
+  } else {
+    out[0] = x[0] + dt * std::exp(th[0]) * (x[0] - x[0] * x[0] * x[0] - x[1] + th[1]) +
+             sq * std::sqrt(std::exp(th[3])) * n[0];
+    out[1] = x[1] + dt * (th[2] * x[0] - x[1] + 1.4) + sq * std::sqrt(std::exp(th[4])) * n[1];
+  }
+}
+
+// hc_sim_step against the double step, and hc_sim_path (with and without observations, H = 0, 1, 7) against the
+// step chained by hand
+int check_sim(int model, int cases) {
+  const int S = model == 0 ? 1 : 2, P = model == 0 ? 3 : model == 1 ? 3 : model == 2 ? 4 : 5;
+  const float dt = model == 0 || model == 2 ? 1.f : 0.1f;
+  int bad = 0;
+  for (int c = 0; c < cases; ++c) {
+    float x[2] = {0.f, 0.f}, th[5] = {0.f, 0.f, 0.f, 0.f, 0.f}, n[2];
+    for (int d = 0; d < S; ++d) x[d] = static_cast<float>(model == 1 ? uniform(50.0, 200.0) : uniform(-1.5, 1.5));
+    for (int p = 0; p < P; ++p) th[p] = static_cast<float>(uniform(-0.5, 0.5));
+    if (model == 1) {
+      th[0] = static_cast<float>(std::log(0.5) + uniform(-0.1, 0.1));
+      th[1] = static_cast<float>(std::log(0.0025) + uniform(-0.1, 0.1));
+      th[2] = static_cast<float>(std::log(0.3) + uniform(-0.1, 0.1));
+    }
+    for (int d = 0; d < 2; ++d) n[d] = static_cast<float>(uniform(-2.0, 2.0));
+    float got[2] = {0.f, 0.f};
+    double ref[2] = {0.0, 0.0};
+    hc_sim_step(model, x, th, dt, n, got);
+    sim_step_ref(model, x, th, dt, n, ref);
+    for (int d = 0; d < S; ++d)
+      if (!(std::fabs(got[d] - ref[d]) <= 1e-5 * std::fmax(1.0, std::fabs(ref[d]) + std::fabs(x[d])))) {
+        std::printf("sim model %d case %d coordinate %d: %.9g vs %.9g\n", model, c, d, got[d], ref[d]);
+        ++bad;
+      }
+    for (int obs = 0; obs < (model == 2 ? 1 : 2); ++obs)
+      for (int H : {0, 1, 7}) {
+        const int NS = obs ? 2 * S : S;
+        const size_t Hs = static_cast<size_t>(H);
+        std::vector<float> nn(Hs * NS), xo(S * Hs), yo(S * Hs);
+        for (float& v : nn) v = static_cast<float>(uniform(-2.0, 2.0));
+        float xe[2] = {-7.f, -7.f};
+        hc_sim_path(model, x, th, dt, 0.5f, H, nn.data(), xo.data(), obs ? yo.data() : nullptr, xe);
+        float cur[2] = {x[0], x[1]};
+        for (int t = 0; t < H; ++t) {
+          float nx[2];
+          const float* nt = nn.data() + static_cast<size_t>(t) * NS;
+          hc_sim_step(model, cur, th, dt, nt, nx);
+          for (int d = 0; d < S; ++d) {
+            cur[d] = nx[d];
+            const size_t at = d * Hs + t;
+            const bool same = xo[at] == cur[d] && (!obs || yo[at] == cur[d] + 0.5f * nt[S + d]);
+            if (!same && std::isfinite(cur[d])) { std::printf("sim path model %d H %d step %d\n", model, H, t); ++bad; }
+          }
+        }
+        for (int d = 0; d < S; ++d)
+          if (std::isfinite(cur[d]) && xe[d] != cur[d]) {
+            std::printf("sim path model %d H %d: x_end\n", model, H);
+            ++bad;
+          }
+      }
+  }
+  return bad;
+}
+
+// an LV row that leaves the positive orthant at its third step: NaN from there on, in x, y and x_end; a start outside
+// it: NaN throughout
+int check_sim_dead() {
+  const float th[3] = {std::log(0.5f), std::log(0.0025f), std::log(0.3f)};
+  const float x0[2] = {0.5f, 100.f};
+  const int H = 6;
+  std::vector<float> nn(static_cast<size_t>(H) * 4, 0.f), xo(2 * H), yo(2 * H);
+  nn[2 * 4] = -30.f;  // step 2: x1 pushed far below zero
+  float xe[2] = {0.f, 0.f};
+  hc_sim_path(1, x0, th, 0.1f, 1.f, H, nn.data(), xo.data(), yo.data(), xe);
+  int bad = 0;
+  for (int d = 0; d < 2; ++d)
+    for (int t = 0; t < H; ++t) {
+      const bool want_nan = t >= 2;
+      if (std::isnan(xo[d * H + t]) != want_nan || std::isnan(yo[d * H + t]) != want_nan) {
+        std::printf("sim dead row: coordinate %d step %d: %g %g\n", d, t, xo[d * H + t], yo[d * H + t]);
+        ++bad;
+      }
+    }
+  if (!std::isnan(xe[0]) || !std::isnan(xe[1])) { std::printf("sim dead row: x_end %g %g\n", xe[0], xe[1]); ++bad; }
+  const float xneg[2] = {-1.f, 100.f};
+  hc_sim_path(1, xneg, th, 0.1f, 1.f, H, nn.data(), xo.data(), nullptr, xe);
+  for (int i = 0; i < 2 * H; ++i)
+    if (!std::isnan(xo[i])) { std::printf("sim dead start: entry %d = %g\n", i, xo[i]); ++bad; }
+  return bad;
+}
+
 }  // namespace
 
 int main() {
@@ -201,9 +311,11 @@ int main() {
   float gx = 0.f;
   const float o = vissm_host_obs(1.5f, 1.0f, 1.f, 0.5f, &gx);
   if (!std::isfinite(o) || std::fabs(gx + 2.f) > 1e-5f) { std::printf("obs_term: gx %g\n", gx); ++bad; }
+  for (int model = 0; model < 4; ++model) bad += check_sim(model, 50);
+  bad += check_sim_dead();
   bad += check_colkey();
   bad += check_select();
-  for (int which = 0; which < 5; ++which) {
+  for (int which = 0; which < 6; ++which) {
     size_t out[2] = {0, 0};
     vissm_host_abi_layout(which, out);
     if (out[0] == 0 || out[1] >= out[0]) { std::printf("abi layout %d: %zu %zu\n", which, out[0], out[1]); ++bad; }

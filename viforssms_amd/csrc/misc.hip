@@ -31,20 +31,6 @@ void set_error(const char* fmt, ...) {
 // (column group, row + offset) so the stream is independent of the launch
 // geometry and of how rows are sharded across ranks.
 // ---------------------------------------------------------------------------
-// Box-Muller on the hardware transcendentals: r = sqrt(-2 ln u1) from v_log_f32 (log2) and
-// v_sqrt_f32, the angle 2 pi u2 through v_sin_f32 / v_cos_f32, whose argument is in revolutions
-// (u2 itself, in (0, 1]) -- no range reduction.  Every kernel that draws the stream uses this.
-__device__ __forceinline__ void box_muller4(u4 r, float (&v)[4]) {
-  constexpr float kM2Ln2 = -1.3862943611198906f;  // -2 ln 2
-  const float r1 = __builtin_amdgcn_sqrtf(kM2Ln2 * __builtin_amdgcn_logf(u01(r.x)));
-  const float r2 = __builtin_amdgcn_sqrtf(kM2Ln2 * __builtin_amdgcn_logf(u01(r.z)));
-  const float t1 = u01(r.y), t2 = u01(r.w);
-  v[0] = r1 * __builtin_amdgcn_cosf(t1);
-  v[1] = r1 * __builtin_amdgcn_sinf(t1);
-  v[2] = r2 * __builtin_amdgcn_cosf(t2);
-  v[3] = r2 * __builtin_amdgcn_sinf(t2);
-}
-
 // One wave per row (kNbW rows per 256-thread block): the base log-prob is a wave reduction, no
 // block barrier.
 // (offset_dev: the row offset read from device memory instead, so a captured graph can advance it)

@@ -920,3 +920,46 @@ def col_order_stats(x: torch.Tensor, ranks: torch.Tensor, dist=None) -> torch.Te
     out = torch.empty(n_ranks, d.n_cols, dtype=torch.float32, device=dev)
     check(lib.vissm_col_select_decode(ctypes.byref(d), ptr(prefix), ptr(out), st), "vissm_col_select_decode")
     return out
+
+
+# ---------------------------------------------------------------------------------------
+# forward simulation (posterior-predictive forecasts)
+# ---------------------------------------------------------------------------------------
+def sde_simulate(model_id: int, theta: torch.Tensor, x_start: torch.Tensor, H: int, dt: float, seed: int, row0: int,
+                 t0: int = 0, obs_std: Optional[float] = None):
+    """Euler-Maruyama paths of one of the four SDEs from per-sample theta [B, P] (raw, as the ELBO takes it) and
+    start states x_start [B, S] (vissm_sde_simulate: one lane per sample, the normals drawn in the kernel).  Returns
+    (x [B, S, H], y [B, S, H] or None, x_end [B, S]); y = x + obs_std * noise when obs_std is given (not SV).  Sample
+    b at step t0 + t consumes entries (t0 + t) NS .. + NS - 1 of the row row0 + b of normal_base(seed, ...) with
+    NS = S (2 S with observations), so a call with t0 > 0 and x_start = an earlier call's x_end continues that
+    simulation bitwise.  A dead sample (state not finite; LV: outside the positive orthant) is NaN from its dying
+    step on.  H = 0: empty x / y and x_end = x_start, no launch."""
+    if model_id not in _lib.MODEL_S:
+        raise _lib.VissmError(f"sde_simulate: unknown model {model_id}")
+    S, P = _lib.MODEL_S[model_id], _lib.MODEL_P[model_id]
+    _require_gpu(theta, x_start)
+    if theta.dtype != torch.float32 or x_start.dtype != torch.float32:
+        raise _lib.VissmError("sde_simulate: fp32 theta and x_start expected")
+    if theta.dim() != 2 or theta.shape[1] != P or x_start.dim() != 2 or tuple(x_start.shape) != (theta.shape[0], S):
+        raise _lib.VissmError(f"sde_simulate: theta [B, {P}] and x_start [B, {S}] expected, got "
+                              f"{tuple(theta.shape)} and {tuple(x_start.shape)}")
+    with_obs = obs_std is not None
+    if with_obs and model_id == _lib.MODEL_SV:
+        raise _lib.VissmError("sde_simulate: no observation model for SV (its first coordinate is the observed series)")
+    B, H, t0 = theta.shape[0], int(H), int(t0)
+    NS = 2 * S if with_obs else S
+    if H < 0 or t0 < 0 or (t0 + H) * NS >= 2 ** 31:
+        raise _lib.VissmError(f"sde_simulate: bad horizon H={H} t0={t0} ((t0 + H) * {NS} must stay below 2^31)")
+    if not 0 <= int(row0) < 2 ** 64:
+        raise _lib.VissmError(f"sde_simulate: row0={row0} outside [0, 2^64)")
+    dev = theta.device
+    x = torch.empty(B, S, H, dtype=torch.float32, device=dev)
+    y = torch.empty(B, S, H, dtype=torch.float32, device=dev) if with_obs else None
+    if H == 0 or B == 0:
+        return x, y, x_start.clone()
+    x_end = torch.empty(B, S, dtype=torch.float32, device=dev)
+    d = _lib.SimDesc(model_id, B, H, t0, NS, float(dt), float(obs_std) if with_obs else 0.0, int(with_obs))
+    check(_lib.load().vissm_sde_simulate(ctypes.byref(d), ctypes.c_uint64(seed & (2 ** 64 - 1)),
+                                         ctypes.c_uint64(int(row0)), ptr(theta), ptr(x_start), ptr(x), ptr(y),
+                                         ptr(x_end), _lib.stream_handle(dev)), "vissm_sde_simulate")
+    return x, y, x_end

@@ -18,7 +18,14 @@ import torch
 
 from . import _lib
 from .nma import Engine, ModelDef, Batch, AdamaxSlots, ScalarLog
-from .summary import DEFAULT_PROBS, column_summary
+from .summary import DEFAULT_PROBS, _check_probs, column_summary
+
+# Philox key of the forecast's normals: the engine's seed xor this (Engine.draw keys eps by the seed itself and the
+# q(theta) base draw by seed ^ 0x5DEECE66D)
+FORECAST_SEED_XOR = 0xF02ECA57
+# device bytes one forecast launch may write per output ([B, S, chunk] fp32): the default chunk is the largest
+# multiple of the kernel's tile under it
+FORECAST_CHUNK_BYTES = 256 << 20
 
 
 @dataclass
@@ -603,6 +610,74 @@ class VISSMBase:
     def save_summary(self, PATH: str, probs=DEFAULT_PROBS) -> Dict[str, np.ndarray]:
         """posterior_summary written as one .npz by rank 0 (every rank computes it: the collectives need them all)."""
         res = self.posterior_summary(probs)
+        if self.dist.rank == 0:
+            d = os.path.dirname(PATH)
+            if d:
+                os.makedirs(d, exist_ok=True)
+            with open(PATH, "wb") as f:
+                np.savez(f, **res)
+        return res
+
+    # ------------------------------------------------------------------ posterior-predictive forecasts
+    def forecast_chunk(self) -> int:
+        """Steps per launch of forecast() by default: [p_local, S, chunk] fp32 stays under FORECAST_CHUNK_BYTES."""
+        steps = FORECAST_CHUNK_BYTES // (4 * _lib.MODEL_S[self.mdef.model_id] * max(self.p_local, 1))
+        return max(_lib.SIM_TILE, steps // _lib.SIM_TILE * _lib.SIM_TILE)
+
+    @torch.no_grad()
+    def forecast(self, horizon: int, probs=DEFAULT_PROBS, obs: bool = False, chunk: Optional[int] = None
+                 ) -> Dict[str, np.ndarray]:
+        """Posterior-predictive forecast: the SDE simulated `horizon` steps past the data on the GPU
+        (ops.sde_simulate), from every sample of the draw of the last window save_paths / posterior_summary visit
+        (same start, same step) -- its theta and its path's last state -- and summarised over the samples of all
+        ranks with summary.column_summary.  forecast/{mean, sd, n_valid} are [S, H], forecast/quantiles [Q, S, H]
+        (S the state's coordinates; 2 for SV, the observed series and its log-volatility); obs=True adds the same
+        four under forecast/obs/ for simulated observations x + obs_std * noise (not SV); forecast/start =
+        target_len(), the index of the first forecast step.  A trajectory that leaves the model's domain is NaN
+        from there on and n_valid counts the rest: the bands condition on survival.  The normals are
+        Philox rows global_step * p + rank * p_local + b under key seed ^ FORECAST_SEED_XOR, so the result does not
+        depend on the number of ranks; `chunk` steps per launch (default forecast_chunk()), chained through the end
+        state, change nothing either.  Every rank takes part in the collectives and gets the same result."""
+        from . import ops
+        H = int(horizon)
+        if H < 0:
+            raise ValueError(f"forecast horizon {horizon} < 0")
+        p = _check_probs(probs)
+        md = self.mdef
+        if obs and md.model_id == _lib.MODEL_SV:
+            raise ValueError("forecast(obs=True): SV has no observation model (its first coordinate is the observed "
+                             "series)")
+        chunk = self.forecast_chunk() if chunk is None else int(chunk)
+        if chunk < 1:
+            raise ValueError(f"forecast chunk {chunk} < 1")
+        last = int(np.arange(0, self.target_len(), self.batch_dims)[-1])
+        x, theta = self.sample_paths_theta(np.tile(last, self.p_local), step=self.global_step)
+        th = theta.detach().float().contiguous()
+        state = x[:, :, -1].float().contiguous()
+        seed = self.engine.seed ^ FORECAST_SEED_XOR
+        row0 = self.global_step * self.p + self.dist.rank * self.p_local
+        S, Q = _lib.MODEL_S[md.model_id], p.size   # the state's coordinates (SV: 2; its mdef.D counts the latent one)
+        groups = ("forecast", "forecast/obs") if obs else ("forecast",)
+        parts = {g: [] for g in groups}
+        for t0 in range(0, H, chunk):
+            m = min(chunk, H - t0)
+            xs, ys, state = ops.sde_simulate(md.model_id, th, state, m, md.dt, seed, row0, t0=t0,
+                                             obs_std=md.obs_std if obs else None)
+            for g, v in zip(groups, (xs, ys)):
+                parts[g].append((m, column_summary(v.view(v.shape[0], S * m), probs, self.dist)))
+        res: Dict[str, np.ndarray] = {"probs": p, "forecast/start": np.asarray(self.target_len(), dtype=np.int64)}
+        for g in groups:
+            for k, dt_ in (("mean", np.float64), ("sd", np.float64), ("n_valid", np.int64)):
+                res[f"{g}/{k}"] = np.concatenate([s[k].reshape(S, m) for m, s in parts[g]] +
+                                                 [np.zeros((S, 0), dtype=dt_)], axis=1)
+            res[f"{g}/quantiles"] = np.concatenate([s["quantiles"].reshape(Q, S, m) for m, s in parts[g]] +
+                                                   [np.zeros((Q, S, 0))], axis=2)
+        return res
+
+    def save_forecast(self, PATH: str, horizon: int, probs=DEFAULT_PROBS, obs: bool = False,
+                      chunk: Optional[int] = None) -> Dict[str, np.ndarray]:
+        """forecast written as one .npz by rank 0 (every rank computes it: the collectives need them all)."""
+        res = self.forecast(horizon, probs, obs, chunk)
         if self.dist.rank == 0:
             d = os.path.dirname(PATH)
             if d:
