@@ -1447,6 +1447,87 @@ __device__ __forceinline__ void fence2() {
 #ifndef VISSM_BWD2_TAIL_NODU
 #define VISSM_BWD2_TAIL_NODU 4
 #endif
+// Input windows staged one unit ahead (docs/DESIGN_HISTORY.md §13).  Every unit of bwd2_kernel and fwd2_kernel opened
+// with the global loads of its two u windows (and upstream-gradient windows), waited for them with nothing else in
+// flight, and stored them into the wave's uwin / gwin rows; the rows are streamed (another sample row per unit), so
+// that wait is a full memory latency per unit.  With the switch on, the windows are double-buffered by the unit's
+// parity and unit n issues unit n + 1's windows as LDS-DMA loads (no register destination: the du variant has none to
+// spare) into the other buffer, right behind the unit's last use of an ordinary load.  Ordering, per wave (the rows are
+// wave-private, no barrier is involved):
+//  * RAW: a unit opens with s_waitcnt vmcnt(0), ahead of its first window read -- a whole unit behind the issue; the
+//    compiler does not count the DMA, so this wait is explicit (stage_wait);
+//  * WAR: the buffer unit n stages into was last read by unit n - 1, whose reads' results were all consumed (lgkmcnt
+//    waits) before unit n began, and a wave's LDS operations complete in order.
+// The window entries at lane >= nu, which the unit's loads stored as zeros, are zeroed once per item in both buffers
+// (no DMA writes them); a ghost partner's gwin row is zeroed by a plain store at the unit's head and gets no DMA.
+// VISSM_STAGE_AHEAD_VAR: 1 the AR bf16 forward, 2 / 4 / 8 the backward's variants without du / with du / fused
+// (NPR = 1 with the theta fold).  On: the du variant (18.98 -> 18.34 ms per AR-cfg launch) and the fused one (20.70 ->
+// 20.30).  Off: the forward -- the staging statement splits the unit's scheduling region and the kernel comes out at
+// 133 registers, three waves per SIMD instead of four (7.08 -> 8.23 ms) -- and the first flow's variant without du
+// (17.11 -> 17.82 ms at every site tried).  Level 0 compiles the earlier instruction streams of all four units
+// (scripts/compare_kernel_asm.py).  No float operation changes: outputs are bitwise those of level 0.
+#ifndef VISSM_STAGE_AHEAD
+#define VISSM_STAGE_AHEAD 1
+#endif
+#ifndef VISSM_STAGE_AHEAD_VAR
+#define VISSM_STAGE_AHEAD_VAR 12
+#endif
+// where a backward unit issues the next unit's windows: 0 behind layer 0's ELU, 2 behind the head backward.  The du
+// variant measured fastest at 0 (18.98 -> 18.34 ms per launch; behind the hidden layer's ELU 18.68, behind the head
+// backward 18.91, ahead of dX 19.17, right behind layer 0's MFMAs 18.36); the fused variant keeps its pair loop free of
+// scratch at 2 only (one reload inside the du section at the other sites).  profiles/r13/ab_explore.txt
+#ifndef VISSM_STAGE_SITE_DU
+#define VISSM_STAGE_SITE_DU 0
+#endif
+#ifndef VISSM_STAGE_SITE_FZ
+#define VISSM_STAGE_SITE_FZ 2
+#endif
+// the LDS byte address of a wave-uniform pointer, in a scalar register
+__device__ __forceinline__ unsigned lds_addr(const void* p) {
+  return __builtin_amdgcn_readfirstlane(
+      static_cast<unsigned>(reinterpret_cast<size_t>((__attribute__((address_space(3))) const void*)p)));
+}
+// Two LDS-DMA loads: LDS[dst_i + 4 lane] = *(float*)((char*)base_i + voff) on the lanes of mask_i (i = 0, 1); all
+// operands but voff wave-uniform.  One statement: M0 (the destination base) and EXEC are set and put back inside it,
+// so the unit stays one basic block.  s_nop 4: the scalar operands may come fresh from a VALU (v_readfirstlane).
+__device__ __forceinline__ void lds_dma_pair(unsigned long long mask0, unsigned long long mask1, unsigned voff,
+                                             const float* base0, const float* base1, unsigned dst0, unsigned dst1) {
+  unsigned keep_m0;
+  unsigned long long keep_exec;
+  asm volatile(
+      "s_nop 4\n\t"
+      "s_mov_b32 %0, m0\n\t"
+      "s_and_saveexec_b64 %1, %2\n\t"
+      "s_mov_b32 m0, %7\n\t"
+      "s_nop 0\n\t"
+      "global_load_lds_dword %4, %5\n\t"
+      "s_and_b64 exec, %1, %3\n\t"
+      "s_mov_b32 m0, %8\n\t"
+      "s_nop 0\n\t"
+      "global_load_lds_dword %4, %6\n\t"
+      "s_mov_b64 exec, %1\n\t"
+      "s_mov_b32 m0, %0"
+      : "=&s"(keep_m0), "=&s"(keep_exec)
+      : "s"(mask0), "s"(mask1), "v"(voff), "s"(base0), "s"(base1), "s"(dst0), "s"(dst1)
+      : "memory", "scc");
+}
+// the lanes below n (n <= 64), or none
+__device__ __forceinline__ unsigned long long lanes_below(int n, bool on) {
+  return on ? (n >= 64 ? ~0ull : (1ull << n) - 1ull) : 0ull;
+}
+// The windows [t0, t0 + n) of rows b0 and b1 (row pitch `pitch`, entries clamped to len - 1 as the units' own loads
+// clamp them) of `src` into the LDS rows win[0], win[1]; `on`: else no lane is active; `both`: else row b1 is left out.
+template <int N>
+__device__ __forceinline__ void stage_windows(const float* src, int pitch, int len, int b0, int b1, int t0, int n,
+                                              int lane, float (*win)[N], bool on, bool both) {
+  const unsigned long long m = lanes_below(n, on);
+  lds_dma_pair(m, both ? m : 0ull, 4u * static_cast<unsigned>(clampi(t0 + lane, len)),
+               src + static_cast<size_t>(b0) * pitch, src + static_cast<size_t>(b1) * pitch, lds_addr(win[0]),
+               lds_addr(win[1]));
+}
+// the head's wait for the windows staged during the previous unit (and for the head's own loads, issued above it)
+__device__ __forceinline__ void stage_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+
 // sched_group_barrier masks
 constexpr int kSgMfma = 0x008, kSgDsRead = 0x100;
 // "N LDS reads, then N groups of M MFMAs" as one pipeline (sync id ID) of the scheduling region; the groups take
@@ -1480,6 +1561,12 @@ __device__ __forceinline__ bf8 tr_frag2(const __bf16* img, int hb, int g, int c)
 // products, whose independent per-position roundings average out.  CPU emulation at the AR-cfg length
 // (scripts/bf16_grad_emul.py): gradient 2.5e-3 (bf16) / 2.2e-3 (bf16x2f: split forward only) -> 7e-5 with SB.
 // NPR = 2 without SB: the bf16x2f host mode's fused last flow (VISSM_PREC_BF16X2_BF16: backward products bf16).
+// the wave's window rows [sample slot][entry] of the unit's buffer (STG: by the unit's parity `par`; otherwise the
+// single buffer, the expression the kernels always had)
+// (pw: the buffer's first row, 0 or the wave count, in a scalar register the compiler takes as opaque: it would
+// otherwise keep every window address of both buffers in registers for the whole item)
+#define VISSM_UW (*(STG ? &uwin[pw + w] : &uwin[w]))
+#define VISSM_GW (*(STGG ? &gwin[pw + w] : &gwin[w]))
 template <bool FZ, bool DU, bool TF, int NPR = 1, bool SB = false>
 __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __restrict__ u, const float* __restrict__ C,
                                                       const float* __restrict__ tht, const float* __restrict__ gout,
@@ -1510,10 +1597,17 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
   __shared__ float dthl[NW2][S][DTH];
   __shared__ __attribute__((aligned(16))) float dths[NW2][4];
   __shared__ float carry[NW2][S][KP2];
-  __shared__ float uwin[NW2][2][UWN];
+  // the windows staged one unit ahead (VISSM_STAGE_AHEAD): the flagship variants; a second uwin buffer (rows NW2 + w:
+  // +4 KB per block), and a second gwin (+1 KB) where it comes from memory (the fused variant's is written by its own
+  // head backward)
+  constexpr bool STG = VISSM_STAGE_AHEAD && NPR == 1 && TF && UWN == 64 &&
+                       (VISSM_STAGE_AHEAD_VAR & (FZ ? 8 : DU ? 4 : 2)) != 0;
+  constexpr bool STGG = STG && !FZ;
+  constexpr int SITE = FZ ? VISSM_STAGE_SITE_FZ : VISSM_STAGE_SITE_DU;
+  __shared__ float uwin[STG ? 2 * NW2 : NW2][2][UWN];
   // the upstream gradient g_mu at p (read by the head backward); NPR = 2 (LDS for the lo planes): then overwritten
   // with g_mu sigma, the du pass-through term, instead of keeping sigma in gsc
-  __shared__ float gwin[NW2][2][P];
+  __shared__ float gwin[STGG ? 2 * NW2 : NW2][2][P];
   __shared__ float gsc[NPR == 2 ? 1 : NW2][2][P];
   __shared__ float dscr[NW2][2][KP2][QW2];
   constexpr bool ZLS = FZ && NPR == 1;  // per-column log sigma sums in LDS
@@ -1587,6 +1681,21 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
   }
   const int m_start = (FZ && chn > 0) ? m_lo - PO : m_lo;
   const int nu = a.k + P;  // u entries a unit reads (stride 1)
+  int par = 0;  // STG: the unit's window buffer
+  if constexpr (STG) {
+    if (lane >= nu) {
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb) {
+        uwin[w][cb][lane] = 0.f;
+        uwin[NW2 + w][cb][lane] = 0.f;
+      }
+    }
+    // the item's first unit
+    stage_windows(u, a.pL, a.L, b_lo, b_lo + (1 < nb ? 1 : 0), m_start, nu, lane, uwin[w], m_start < m_hi, true);
+    if constexpr (!FZ)
+      stage_windows(gout, a.pLo, a.Lout, b_lo, b_lo + (1 < nb ? 1 : 0), m_start, P, lane, gwin[w], m_start < m_hi,
+                    1 < nb);
+  }
   for (int m0 = m_start; m0 < m_hi; m0 += PO) {
     const bool discard = FZ && m0 < m_lo;
     const int nP = discard ? 0 : min(PO, m_hi - m0), t0 = m0;
@@ -1605,21 +1714,50 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
       const bool two = bl + 1 < nb;  // wave-uniform; else the second slot is a ghost
       const int blv[2] = {bl, two ? bl + 1 : bl};
       const int bv[2] = {b_lo + blv[0], b_lo + blv[1]};
+      int pw = 0;
+      if constexpr (STG) {
+        // RAW: this unit's windows were issued during the previous unit (the item's first: in the prologue); the wait
+        // stands before every read of the buffer.  At the unit's top, above the issue of the C and theta rows: the
+        // statement bounds a scheduling region, and the head's loads stay in one region with their consumers.
+        stage_wait();
+        pw = par * NW2;
+        asm volatile("" : "+s"(pw));
+      }
+      // STG: the next unit's windows into the other buffer: the same tile's next pair, or the next tile's first pair;
+      // the item's last unit stages nothing (no lane active, the addresses those of this unit).  Called behind layer 0
+      // -- its MFMAs are the last consumers of this unit's ordinary loads (the C rows as their accumulator input, the
+      // theta rows in their B operand; the fused variant's observations are taken at the head) -- so that no wait for
+      // such a load drains the DMA before the next unit's, and at a phase fence of the fenced variants (the statement
+      // bounds a scheduling region as a fence does).  WAR: the other buffer's last reads (the previous unit's) were
+      // consumed before this unit began.
+      const auto stage_next = [&]() {
+        const bool lastp = bl + 2 >= nb, more = !lastp || m0 + PO < m_hi;
+        const int ms = (lastp && more) ? m0 + PO : m0, bs = lastp ? (more ? 0 : bl) : bl + 2;
+        const int b0 = b_lo + bs, b1 = b_lo + (bs + 1 < nb ? bs + 1 : bs);
+        __builtin_amdgcn_sched_barrier(0);
+        stage_windows(u, a.pL, a.L, b0, b1, ms, nu, lane, uwin[NW2 - pw + w], more, true);
+        if constexpr (STGG)
+          stage_windows(gout, a.pLo, a.Lout, b0, b1, ms, P, lane, gwin[NW2 - pw + w], more, bs + 1 < nb);
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      (void)stage_next;
       // ---- inputs: the two u windows (and upstream-gradient windows), the shared C rows + each theta row
       f4 X[2][4];
       bf8 tfr[2];
       float fz_yp = fz_yt, fz_bp = fz_bt, fz_zc[2] = {0.f, 0.f};
       {
-        float uv[2], gv[2] = {0.f, 0.f};
+        float uv[2] = {0.f, 0.f}, gv[2] = {0.f, 0.f};
+        if constexpr (!STG) {
 #pragma unroll
-        for (int cb = 0; cb < 2; ++cb) {
-          const float* ub = u + static_cast<size_t>(bv[cb]) * a.pL;
-          uv[cb] = lane < nu ? ub[clampi(t0 + lane, a.L)] : 0.f;
-          if constexpr (!FZ) {
-            if (lane < P) gv[cb] = gout[static_cast<size_t>(bv[cb]) * a.pLo + clampi(t0 + lane, a.Lout)];
+          for (int cb = 0; cb < 2; ++cb) {
+            const float* ub = u + static_cast<size_t>(bv[cb]) * a.pL;
+            uv[cb] = lane < nu ? ub[clampi(t0 + lane, a.L)] : 0.f;
+            if constexpr (!FZ) {
+              if (lane < P) gv[cb] = gout[static_cast<size_t>(bv[cb]) * a.pLo + clampi(t0 + lane, a.Lout)];
+            }
           }
+          if (!two) gv[1] = 0.f;
         }
-        if (!two) gv[1] = 0.f;
         const f4* crow = reinterpret_cast<const f4*>(C + static_cast<size_t>(m0 + clampi(c, nZ)) * HP) + g;
         f4 cr[4], tr[2][4];
         if constexpr (TF) {  // the theta fold: the pair's theta rows of the layer-0 B operand (lane groups 2, 3)
@@ -1636,10 +1774,21 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
           }
         }
         __builtin_amdgcn_sched_barrier(0);
+        if constexpr (STG) {
+          if constexpr (!FZ) {
+            if (!two && lane < P) VISSM_GW[1][lane] = 0.f;  // the ghost's row: no DMA was issued into it
+          } else {
+            // the tile's observations (loaded above the pair loop) count as used here: their wait in the tile's
+            // first head backward would drain the DMA issued before it
+            asm volatile("" : "+v"(fz_yp), "+v"(fz_bp));
+          }
+        }
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb) {
-          if (UWN == 64 || lane < UWN) uwin[w][cb][lane] = uv[cb];
-          if (lane < P) gwin[w][cb][lane] = gv[cb];
+          if constexpr (!STG) {
+            if (UWN == 64 || lane < UWN) VISSM_UW[cb][lane] = uv[cb];
+            if (lane < P) VISSM_GW[cb][lane] = gv[cb];
+          }
 #pragma unroll
           for (int rb = 0; rb < 4; ++rb) X[cb][rb] = TF ? cr[rb] : cr[rb] + tr[cb][rb];
         }
@@ -1657,7 +1806,7 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
         f4 acc[2][4];
         fence2<FZ || (!DU && VISSM_NODU_FENCES)>();
         const int gu = (LOF && g == 1) ? 0 : g;  // LOF: lane group 1's K rows repeat the taps 0..7 (lo weights)
-        Fr8<NP> uf[2] = {u_frag<NP>(uwin[w][0], 1, 0, gu, c), u_frag<NP>(uwin[w][1], 1, 0, gu, c)};
+        Fr8<NP> uf[2] = {u_frag<NP>(VISSM_UW[0], 1, 0, gu, c), u_frag<NP>(VISSM_UW[1], 1, 0, gu, c)};
         if constexpr (TF) {
           if (g >= 2) {
             uf[0].h = tfr[0];
@@ -1707,6 +1856,7 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
             }
           }
         fence2<FZ || (!DU && VISSM_NODU_FENCES)>();
+        if constexpr (STG && SITE == 0) stage_next();
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb) {
           if (g == 3) X[cb][3][3] = 1.f;  // the ones row: bias of the hidden layer
@@ -1767,7 +1917,7 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb)
           if (g == 3) X[cb][3][3] = 1.f;
-        if constexpr (FZ && (TAIL & 32) != 0) uk_e = uwin[w][g >> 1][c + a.k];
+        if constexpr (FZ && (TAIL & 32) != 0) uk_e = VISSM_UW[g >> 1][c + a.k];
         if constexpr (AH) {  // both WH fragments, then the four MFMAs
           const bf8 wh[2] = {sh.img[fh][0][lane], sh.img[fh + 1][0][lane]};
 #pragma unroll
@@ -1810,7 +1960,7 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
         const bool hv = hs == 0 || two;             // not the ghost
         const float mu_h = hs ? mu[1] : mu[0], rr_h = hs ? rr[1] : rr[0];
         const float sig_h = softplus_fast(rr_h) + 1e-10f;
-        const float uk = (TAIL & 32) ? uk_e : uwin[w][hs][c + a.k];
+        const float uk = (TAIL & 32) ? uk_e : VISSM_UW[hs][c + a.k];
         const float x = uk * sig_h + mu_h;
         float xp = row_prev(x);
         const float xn = row_next(x);
@@ -1829,7 +1979,7 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
         const float gmu_h = hv ? -fz.scale * de : 0.f;
         const float lsg = (t0 + c >= a.Lout - a.n_logsig) ? __builtin_amdgcn_logf(sig_h) * kLn2 : 0.f;
         if ((g & 1) == 0) {  // lane groups 0 (A) and 2 (B)
-          if constexpr (NPR == 1) gwin[w][hs][c] = gmu_h;  // the upstream-gradient window the du section reads
+          if constexpr (NPR == 1) VISSM_GW[hs][c] = gmu_h;  // the upstream-gradient window the du section reads
           if (pv && hv) {
             if constexpr (!(VISSM_ABL_STORES & 1)) fz.x[static_cast<size_t>(b_lo + bl2) * (fz.M + 1) + t] = x;
             if constexpr (ZLS) zls[w][bl2][c] += lsg;
@@ -1841,7 +1991,7 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
         const float gr_h = dsig * sigmoid_fast(rr_h);
         if ((g & 1) == 0) {
           if constexpr (NPR == 2) {
-            if constexpr (DU) gwin[w][hs][c] = gmu_h * sig_h;  // (after the reads of g_mu above: LDS order)
+            if constexpr (DU) VISSM_GW[hs][c] = gmu_h * sig_h;  // (after the reads of g_mu above: LDS order)
           } else {
             gsc[w][hs][c] = sig_h;
           }
@@ -1867,17 +2017,17 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb) {
           sig[cb] = softplus_fast(rr[cb]) + 1e-10f;
-          gmu[cb] = pv ? gwin[w][cb][c] : 0.f;
+          gmu[cb] = pv ? VISSM_GW[cb][c] : 0.f;
         }
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb) {
           const float dl = lane_f(ldl, blv[cb]);
-          float dsig = gmu[cb] * uwin[w][cb][c + a.k];
+          float dsig = gmu[cb] * VISSM_UW[cb][c + a.k];
           if (pv && (cb == 0 || two) && t0 + c >= a.Lout - a.n_logsig) dsig += dl * rcp_f(sig[cb]);
           gr[cb] = dsig * sigmoid_fast(rr[cb]);
           if (g == 0) {
             if constexpr (NPR == 2) {
-              if constexpr (DU) gwin[w][cb][c] = gmu[cb] * sig[cb];  // (after the reads of g_mu above: LDS order)
+              if constexpr (DU) VISSM_GW[cb][c] = gmu[cb] * sig[cb];  // (after the reads of g_mu above: LDS order)
             } else {
               gsc[w][cb][c] = sig[cb];
             }
@@ -1892,6 +2042,7 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
         }
       }
       fence2<FZ || (!DU && VISSM_NODU_FENCES)>();
+      if constexpr (STG && SITE == 2) stage_next();
       // dW_head[h][o] += sum over both samples' positions of I_1[h][p] G[o][p] (K = 32): block 3 of the same
       // fragments is the B operand (its columns 5, 6 are the G rows)
       // (read ahead: the I_1 fragments are only ISSUED here -- before the dZ image's put_image into the same slot
@@ -2006,7 +2157,7 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
       // passes under the elu' multiplies instead of in front of the packing that feeds the dW_eps MFMAs
       bf8 uaf_e = {};
       if constexpr ((TAIL & 4) != 0) {
-        const Fr4<NP> ua = ua_frag<NP>(uwin[w][0], 1, 0, g, c), ub = ua_frag<NP>(uwin[w][1], 1, 0, g, c);
+        const Fr4<NP> ua = ua_frag<NP>(VISSM_UW[0], 1, 0, g, c), ub = ua_frag<NP>(VISSM_UW[1], 1, 0, g, c);
         uaf_e = cat8(ua.h, ub.h);
       }
       // dA0 = dX * elu'(I_0) (I_0 from the registers the forward left: the image's bf16 values)
@@ -2087,7 +2238,7 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
       const auto du_terms = [&]() {
         const int cbq = lane >> 5, q = lane & 31;
         const int oqc = min(max(q - a.k, 0), P - 1);
-        dug = gwin[w][cbq][oqc];
+        dug = VISSM_GW[cbq][oqc];
         dus = gsc[w][cbq][oqc];
         duc = carry[w][cbq ? blv[1] : blv[0]][q & (KP2 - 1)];
       };
@@ -2099,7 +2250,7 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
         const unsigned one2 = 0x3F803F80u;
         bf8 uaf = uaf_e;
         if constexpr ((TAIL & 4) == 0) {
-          const Fr4<NP> ua = ua_frag<NP>(uwin[w][0], 1, 0, g, c), ub = ua_frag<NP>(uwin[w][1], 1, 0, g, c);
+          const Fr4<NP> ua = ua_frag<NP>(VISSM_UW[0], 1, 0, g, c), ub = ua_frag<NP>(VISSM_UW[1], 1, 0, g, c);
           uaf = cat8(ua.h, ub.h);
         }
         // one B operand for dW_eps^T (columns j < 8: the u windows) and the d theta of the pair's two samples
@@ -2174,7 +2325,7 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
             if (q < a.k) v += duc;
           } else {
             if (oq2 >= 0 && oq2 < nP)
-              v += NPR == 2 ? gwin[w][cbq][oq2] : gwin[w][cbq][oq2] * gsc[w][cbq][oq2];
+              v += NPR == 2 ? VISSM_GW[cbq][oq2] : VISSM_GW[cbq][oq2] * gsc[w][cbq][oq2];
             if (q < a.k) v += carry[w][blq][q];
           }
         }
@@ -2189,6 +2340,7 @@ __global__ __launch_bounds__(NT2, 2) void bwd2_kernel(KArgs a, const float* __re
           }
         }
       }
+      if constexpr (STG) par ^= 1;
     }
     // tile done: its dC over the group (both samples of every pair)
     if (c < nP && !(VISSM_ABL_STORES & 4)) {
@@ -2304,7 +2456,10 @@ __global__ __launch_bounds__(64 * NWF, 2) void fwd2_kernel(KArgs a, const float*
                                                                   const u4* __restrict__ thf) {
   constexpr int KB = (JB + 1) / 2;  // layer-0 K blocks (k > 32: two, a 128-entry u window)
   __shared__ Shared<NH, KB, JB, NP> sh;
-  __shared__ float uwin[NWF][2][64 * KB];
+  // the u windows staged one unit ahead (VISSM_STAGE_AHEAD, above bwd2_kernel): the AR bf16 forward, two buffers
+  constexpr bool STG = VISSM_STAGE_AHEAD && (VISSM_STAGE_AHEAD_VAR & 1) != 0 && TF && NP == 1 && NH == 1 && JB == 1 &&
+                       NWF == NW && !LOF;
+  __shared__ float uwin[STG ? 2 * NWF : NWF][2][64 * KB];  // STG: the second buffer in rows NWF + w
   load_shared<NH, KB, JB, NP, 64 * NWF>(sh, img, cst);
   {  // static wave priority = dispatch round mod 4 (as fwd_kernel)
     const int r = __builtin_amdgcn_readfirstlane(blockIdx.x / a.ncu) & 3;
@@ -2357,6 +2512,18 @@ __global__ __launch_bounds__(64 * NWF, 2) void fwd2_kernel(KArgs a, const float*
   const int ss = NH == 1 ? 1 : a.s;
   const bool swp = NH == 1 ? false : a.swap_out != 0;
   const int nu = ss * P + a.k;  // u entries a unit reads (<= 64 KB)
+  int par = 0;  // STG: the unit's window buffer
+  if constexpr (STG) {
+    if (lane >= nu) {  // the entries no DMA writes: zeros, as the unit's own loads stored them
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb) {
+        uwin[w][cb][lane] = 0.f;
+        uwin[NWF + w][cb][lane] = 0.f;
+      }
+    }
+    // the item's first unit
+    stage_windows(u, a.pL, a.L, b_lo, b_lo + (1 < nb ? 1 : 0), m_lo, nu, lane, uwin[w], nb > 0 && m_lo < m_hi, true);
+  }
   for (int bl = 0; bl < nb; bl += 2) {
     const bool two = bl + 1 < nb;
     const int bv[2] = {b_lo + bl, b_lo + (two ? bl + 1 : bl)};
@@ -2369,13 +2536,24 @@ __global__ __launch_bounds__(64 * NWF, 2) void fwd2_kernel(KArgs a, const float*
     for (int m0 = m_lo; m0 < m_hi; m0 += P) {
       const int nP = min(P, m_hi - m0), t0 = ss * m0;
       f4 X[2][4];
+      int pw = 0;
+      if constexpr (STG) {
+        // RAW: this unit's windows were issued during the previous unit (the item's first: in the prologue); the wait
+        // stands before every read of the buffer (at the unit's top: the statement bounds a scheduling region, and
+        // the C rows' loads stay in one region with the MFMAs that take them)
+        stage_wait();
+        pw = par * NWF;
+        asm volatile("" : "+s"(pw));
+      }
       {
         float uv[2][KB];
+        if constexpr (!STG) {
 #pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
+          for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
-          for (int i = 0; i < KB; ++i)
-            uv[cb][i] = 64 * i + lane < nu ? u[static_cast<size_t>(bv[cb]) * a.pL + clampi(t0 + 64 * i + lane, a.L)] : 0.f;
+            for (int i = 0; i < KB; ++i)
+              uv[cb][i] = 64 * i + lane < nu ? u[static_cast<size_t>(bv[cb]) * a.pL + clampi(t0 + 64 * i + lane, a.L)] : 0.f;
+        }
         const f4* crow = reinterpret_cast<const f4*>(C + static_cast<size_t>(m0 + clampi(c, nP)) * HP) + g;
         f4 cr[4], tr[2][4];
 #pragma unroll
@@ -2390,8 +2568,10 @@ __global__ __launch_bounds__(64 * NWF, 2) void fwd2_kernel(KArgs a, const float*
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb) {
+          if constexpr (!STG) {
 #pragma unroll
-          for (int i = 0; i < KB; ++i) uwin[w][cb][64 * i + lane] = uv[cb][i];
+            for (int i = 0; i < KB; ++i) VISSM_UW[cb][64 * i + lane] = uv[cb][i];
+          }
 #pragma unroll
           for (int rb = 0; rb < 4; ++rb) X[cb][rb] = TF ? cr[rb] : cr[rb] + tr[cb][rb];
         }
@@ -2401,7 +2581,7 @@ __global__ __launch_bounds__(64 * NWF, 2) void fwd2_kernel(KArgs a, const float*
 #pragma unroll
         for (int kb = 0; kb < KB; ++kb) {
           const int gu = (LOF && g == 1) ? 0 : g;  // LOF: lane group 1's K rows repeat the taps 0..7 (lo weights)
-          bf8 uf[2] = {u_frag<1>(uwin[w][0], ss, kb, gu, c).h, u_frag<1>(uwin[w][1], ss, kb, gu, c).h};
+          bf8 uf[2] = {u_frag<1>(VISSM_UW[0], ss, kb, gu, c).h, u_frag<1>(VISSM_UW[1], ss, kb, gu, c).h};
           if constexpr (TF) {
             if (g >= 2) {
               uf[0] = tfr[0];
@@ -2421,6 +2601,18 @@ __global__ __launch_bounds__(64 * NWF, 2) void fwd2_kernel(KArgs a, const float*
             }
           }
         }
+      }
+      if constexpr (STG) {
+        // The next unit's windows into the other buffer: the pair's next tile, or the next pair's first tile; the
+        // item's last unit stages nothing.  Issued behind the layer-0 MFMAs, the last consumers of the unit's ordinary
+        // loads (the C rows; the pair's theta rows), so that no wait for such a load drains the DMA before the next
+        // head's.  WAR: the other buffer's last reads (the previous unit's output rows) were consumed in that unit.
+        const bool lastt = m0 + P >= m_hi, more = !lastt || bl + 2 < nb;
+        const int bs = (lastt && more) ? bl + 2 : bl, ms = lastt ? (more ? m_lo : m0) : m0 + P;
+        __builtin_amdgcn_sched_barrier(0);
+        stage_windows(u, a.pL, a.L, b_lo + bs, b_lo + (bs + 1 < nb ? bs + 1 : bs), ms, nu, lane,
+                      uwin[NWF - pw + w], more, true);
+        __builtin_amdgcn_sched_barrier(0);
       }
 #pragma unroll
       for (int cb = 0; cb < 2; ++cb)
@@ -2484,14 +2676,15 @@ __global__ __launch_bounds__(64 * NWF, 2) void fwd2_kernel(KArgs a, const float*
           const float sg = softplus_fast(d[cb][1]) + 1e-10f;
           const int oq = ss * c + (ss - 1), o = t0 + oq;
           float* ob = u_next + static_cast<size_t>(bv[cb]) * a.pLo;
-          ob[swp ? (o ^ 1) : o] = uwin[w][cb][oq + a.k] * sg + d[cb][0];
+          ob[swp ? (o ^ 1) : o] = VISSM_UW[cb][oq + a.k] * sg + d[cb][0];
           if (ss == 2) {  // the even outputs pass through (lotka_volterra_partial.py:97-104)
             const int oe = t0 + 2 * c;
-            ob[swp ? (oe ^ 1) : oe] = uwin[w][cb][2 * c + a.k];
+            ob[swp ? (oe ^ 1) : oe] = VISSM_UW[cb][2 * c + a.k];
           }
           if (o >= a.Lout - a.n_logsig) ls[cb] += __builtin_amdgcn_logf(sg) * kLn2;
         }
       }
+      if constexpr (STG) par ^= 1;
     }
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb) {
@@ -2500,6 +2693,9 @@ __global__ __launch_bounds__(64 * NWF, 2) void fwd2_kernel(KArgs a, const float*
     }
   }
 }
+
+#undef VISSM_UW
+#undef VISSM_GW
 
 // ---------------------------------------------------------------------------
 // backward kernel for three hidden layers (LV / SV / FHN heads, BN affine folded), two samples per unit
