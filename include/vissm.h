@@ -64,6 +64,15 @@ const char* vissm_build_flags(void);
  * Base noise: init_dist.slp (AR.py:24-35; lotka_volterra_partial.py:25-36).
  * eps[b][j] ~ N(0,1) from counter-based Philox4x32-10 keyed by (seed, offset+b),
  * base_lp[b] = sum_{j >= L - n_last} log N(eps[b][j]; 0, 1).
+ *
+ * The stream, bit for bit (tests/philox_ref.py restates it from the paper; the integer part is
+ * csrc/rng_math.hpp): with r = offset + b (64-bit, wrapping) and g = j / 4,
+ *   (x, y, z, w) = philox4x32_10(ctr = (g, 0, lo32(r), hi32(r)), key = (lo32(seed), hi32(seed))),
+ *   u_v = ((v >> 8) + 1) * 2^-24 for each word v, so u in (0, 1], exact in fp32,
+ *   columns 4g .. 4g+3 = (r1 cos 2 pi u_y, r1 sin 2 pi u_y, r2 cos 2 pi u_w, r2 sin 2 pi u_w),
+ *   r1 = sqrt(-2 ln u_x), r2 = sqrt(-2 ln u_z);
+ * a last group cut by L keeps its first L - 4g columns.  The stream does not depend on B, L, the launch
+ * geometry or how rows are sharded over ranks.
  * ------------------------------------------------------------------------- */
 int vissm_normal_base(uint64_t seed, uint64_t offset, float* eps, float* base_lp,
                       int32_t B, int32_t L, int32_t n_last, void* stream);

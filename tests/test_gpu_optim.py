@@ -1,7 +1,14 @@
 """optimisers.adamax.AdamaxOptimizer (the drop-in facade of optimisers/adamax.py:11-61) on the HIP kernels,
 against the oracle's clip_by_global_norm + adamax_update (AR.py:230-234, optimisers/adamax.py:42-58)
 over several steps: contiguous, non-contiguous (a transposed view) and fp16 variables in one call,
-with and without the global-norm clip, and the in-place path for consecutive views of one buffer."""
+with and without the global-norm clip, and the in-place path for consecutive views of one buffer.
+
+Below that, the kernels' own edges, called on raw buffers: vissm_sqnorm and AdamaxKernel.step at sizes where their
+grid-stride loops make a second trip (n > 1024 * 1024 for the norm partials, n > 2048 * 256 for the update), from base
+pointers that are not 16-byte aligned, at n = 0, and with a gradient whose norm overflows fp32 but not the double
+the kernel sums in."""
+
+import numpy as np
 import pytest
 import torch
 
@@ -94,3 +101,111 @@ def test_facade_slots_follow_changing_groupings():
     for var, slots in ((a, sa[0]), (b, sb[0])):
         assert torch.allclose(opt.get_slot(var, "v").double().cpu(), slots[0], rtol=1e-5, atol=1e-6)
         assert torch.allclose(opt.get_slot(var, "m").double().cpu(), slots[1], rtol=1e-5, atol=1e-6)
+
+
+# ---- vissm_sqnorm ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [0, 1, 3, 4, 5, 1023, 1025, 2 ** 20 + 7, 3 * 2 ** 20 + 1])
+def test_sqnorm_matches_float64_sum(n):
+    """The squares are summed in double and cast once, so the result is the float64 sum to one fp32 rounding
+    (rtol 2^-23); a base pointer 1, 2 or 3 floats off a 256-byte boundary never takes the float4 path."""
+    from viforssms_amd import _lib
+    lib = _lib.load()
+    st = _lib.stream_handle(torch.device(DEV))
+    g = torch.Generator(device=DEV).manual_seed(n + 1)
+    big = torch.randn(n + 8, generator=g, device=DEV) * 3
+    assert big.data_ptr() % 256 == 0
+    wsz = lib.vissm_adamax_workspace_size(n)
+    ws = torch.empty(wsz, dtype=torch.uint8, device=DEV)
+    for off in (0, 1, 2, 3):
+        x = big[off:off + n]
+        out = torch.full((3,), -7.0, device=DEV)
+        _lib.check(lib.vissm_sqnorm(big.data_ptr() + 4 * off, n, out.data_ptr() + 4, ws.data_ptr(), wsz, st),
+                   "vissm_sqnorm")
+        torch.cuda.synchronize()
+        got = out.cpu().numpy()
+        ref = float((x.double() ** 2).sum().item())
+        assert got[0] == -7.0 and got[2] == -7.0
+        if n == 0:
+            assert got[1] == 0.0 and not np.signbit(got[1])
+        else:
+            assert abs(float(got[1]) - ref) <= 2.0 ** -23 * ref, (n, off, float(got[1]), ref)
+
+
+# ---- clip + Adamax at a second grid-stride trip, from unaligned views ---------------------------------------
+N_BIG = 2 ** 20 + 7
+
+
+def _offset_views(tensors):
+    """each tensor copied into a view that starts one float past its allocation: 4-byte, not 16-byte aligned"""
+    out = []
+    for t in tensors:
+        buf = torch.empty(t.numel() + 1, dtype=torch.float32, device=DEV)
+        view = buf[1:]
+        view.copy_(t.float())
+        assert view.data_ptr() % 16 == 4
+        out.append(view)
+    return out
+
+
+@pytest.mark.parametrize("clip", [0.0, 50.0])
+def test_adamax_kernel_second_trip_unaligned_views(clip):
+    from viforssms_amd.ops import AdamaxKernel
+    g = torch.Generator().manual_seed(11)
+    n = N_BIG
+    p = torch.randn(n, generator=g, dtype=torch.float64)
+    gr = torch.randn(n, generator=g, dtype=torch.float64) * 3
+    v = torch.randn(n, generator=g, dtype=torch.float64) * 0.1
+    m = torch.rand(n, generator=g, dtype=torch.float64) + 0.01
+    p, gr, v, m = (t.float().double() for t in (p, gr, v, m))             # what the kernel is given, exactly
+    k = AdamaxKernel(n, DEV)
+    P, G, V, Mm = _offset_views((p, gr, v, m))
+    gn = k.step(P, G, V, Mm, 1e-3, 0.95, 0.999, 1e-8, clip)
+    torch.cuda.synchronize()
+    gg = [gr]
+    if clip > 0:
+        gg, _ = O.clip_by_global_norm([gr], clip)
+    rp, rv, rm = O.adamax_update(p, gg[0], v, m, 1e-3, 0.95, 0.999)
+    assert abs(gn.item() - gr.norm().item()) <= 1e-5 * gr.norm().item()
+    assert torch.allclose(P.double().cpu(), rp, rtol=1e-6, atol=1e-6)
+    assert torch.allclose(V.double().cpu(), rv, rtol=1e-5, atol=1e-6)
+    assert torch.allclose(Mm.double().cpu(), rm, rtol=1e-5, atol=1e-6)
+    assert torch.equal(G.double().cpu(), gr)                              # the gradient is read only
+    # the guarded step with a finite gradient: nothing skipped, bitwise the unguarded result
+    k2 = AdamaxKernel(n, DEV)
+    P2, G2, V2, M2 = _offset_views((p, gr, v, m))
+    gn2 = k2.step(P2, G2, V2, M2, 1e-3, 0.95, 0.999, 1e-8, clip, guard=True)
+    torch.cuda.synchronize()
+    assert k2.skipped.item() == 0
+    for a, b in ((P, P2), (V, V2), (Mm, M2), (gn, gn2)):
+        assert torch.equal(a.view(torch.int32), b.view(torch.int32))
+
+
+def test_guarded_step_with_a_norm_that_overflows_fp32():
+    """2^20 + 7 gradient entries of +-3e38: the squares sum to 9.4e82 in the double the kernel carries, the norm is
+    3.07e41 -- finite as a double, infinite as a float.  What the kernel does, pinned here: the guard tests the double
+    norm, so the step is not skipped (skipped stays 0) and applies with scale = clip / norm computed in double
+    (1.6e-40, a subnormal float: about 17 significant bits, a relative 4e-6 on the scaled gradient, inside the bars
+    below); only the reported fp32 norm is +inf.  The oracle's float64 clip + Adamax is the reference."""
+    from viforssms_amd.ops import AdamaxKernel
+    g = torch.Generator().manual_seed(12)
+    n, clip = N_BIG, 50.0
+    p = torch.randn(n, generator=g, dtype=torch.float64).float().double()
+    sign = (torch.rand(n, generator=g) < 0.5).double() * 2 - 1
+    gr = (sign * 3e38).float().double()
+    v = (torch.randn(n, generator=g, dtype=torch.float64) * 0.1).float().double()
+    m = (torch.rand(n, generator=g, dtype=torch.float64) + 0.01).float().double()
+    norm64 = torch.sqrt((gr ** 2).sum()).item()
+    assert np.isfinite(norm64) and norm64 > float(np.finfo(np.float32).max)
+    k = AdamaxKernel(n, DEV)
+    P, G, V, Mm = _offset_views((p, gr, v, m))
+    gn = k.step(P, G, V, Mm, 1e-3, 0.95, 0.999, 1e-8, clip, guard=True)
+    torch.cuda.synchronize()
+    assert k.skipped.item() == 0
+    assert gn.item() == float("inf")
+    gg, gn_ref = O.clip_by_global_norm([gr], clip)
+    assert torch.isfinite(gn_ref) and torch.isfinite(gg[0]).all()
+    rp, rv, rm = O.adamax_update(p, gg[0], v, m, 1e-3, 0.95, 0.999)
+    assert torch.isfinite(P).all() and torch.isfinite(V).all() and torch.isfinite(Mm).all()
+    assert torch.allclose(P.double().cpu(), rp, rtol=1e-6, atol=1e-6)
+    assert torch.allclose(V.double().cpu(), rv, rtol=1e-5, atol=1e-6)
+    assert torch.allclose(Mm.double().cpu(), rm, rtol=1e-5, atol=1e-6)

@@ -7,6 +7,7 @@
 #include <cstdio>
 
 #include "../../include/vissm.h"
+#include "rng_math.hpp"
 
 namespace vissm {
 
@@ -34,37 +35,9 @@ static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream
 static inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
 // ---------------------------------------------------------------------------
-// Philox4x32-10 (Salmon et al. 2011), counter = (lo(ctr), hi(ctr), lo(sub), hi(sub)),
-// key = seed.  Box-Muller on the 4 outputs gives 4 N(0,1) values.
+// Philox4x32-10 and u01 (rng_math.hpp, shared with the host checks); Box-Muller on the 4 outputs gives
+// 4 N(0,1) values.
 // ---------------------------------------------------------------------------
-struct u4 { uint32_t x, y, z, w; };
-
-__device__ __forceinline__ u4 philox4x32_10(u4 c, uint32_t k0, uint32_t k1) {
-  const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
-  const uint32_t W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    // one 32x32 -> 64-bit product per word (v_mad_u64_u32) instead of separate hi / lo multiplies
-    const uint64_t p0 = static_cast<uint64_t>(M0) * c.x, p1 = static_cast<uint64_t>(M1) * c.z;
-    const uint32_t hi0 = static_cast<uint32_t>(p0 >> 32), lo0 = static_cast<uint32_t>(p0);
-    const uint32_t hi1 = static_cast<uint32_t>(p1 >> 32), lo1 = static_cast<uint32_t>(p1);
-    u4 n;
-    n.x = hi1 ^ c.y ^ k0;
-    n.y = lo1;
-    n.z = hi0 ^ c.w ^ k1;
-    n.w = lo0;
-    c = n;
-    k0 += W0;
-    k1 += W1;
-  }
-  return c;
-}
-
-__device__ __forceinline__ float u01(uint32_t x) {
-  // (0, 1]: never 0 so log() is finite
-  return (static_cast<float>(x >> 8) + 1.0f) * (1.0f / 16777216.0f);
-}
-
 // Box-Muller on the hardware transcendentals: r = sqrt(-2 ln u1) from v_log_f32 (log2) and
 // v_sqrt_f32, the angle 2 pi u2 through v_sin_f32 / v_cos_f32, whose argument is in revolutions
 // (u2 itself, in (0, 1]) -- no range reduction.  Every kernel that draws the stream uses this.

@@ -1,6 +1,7 @@
 // Host (CPU) build of elbo_math.hpp so the CPU test-suite can check the
 // hand-derived transition gradients against the oracle's autograd without a GPU,
-// and of sim_math.hpp (the forecast kernel's Euler-Maruyama steps) against a float64 restatement.
+// of sim_math.hpp (the forecast kernel's Euler-Maruyama steps) against a float64 restatement,
+// and of rng_math.hpp (Philox4x32-10 and u01) against tests/philox_ref.py.
 // Not part of the product path: libvissm_hostcheck.so is loaded only by tests/.
 #include <cstddef>
 
@@ -8,6 +9,7 @@
 #include "elbo_math.hpp"
 #include "colstat_math.hpp"
 #include "sim_math.hpp"
+#include "rng_math.hpp"
 
 extern "C" {
 
@@ -53,6 +55,15 @@ void hc_sim_path(int model, const float* x_start, const float* th, float dt, flo
 }
 
 int hc_sim_alive(int model, const float* x) { return vissm::sim::alive(model, x) ? 1 : 0; }
+
+// The base noise's integer generator (rng_math.hpp: the code normal_base_kernel, normal_base_short_kernel and the
+// forecast kernel run): one Philox4x32-10 block, and the map of an output word to a uniform in (0, 1]
+void hc_philox(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
+  const vissm::u4 r = vissm::philox4x32_10(vissm::u4{ctr[0], ctr[1], ctr[2], ctr[3]}, key[0], key[1]);
+  out[0] = r.x; out[1] = r.y; out[2] = r.z; out[3] = r.w;
+}
+
+float hc_u01(uint32_t w) { return vissm::u01(w); }
 
 // the C ABI's struct layouts as the C compiler sees them (the ctypes mirrors in viforssms_amd/_lib.py are
 // checked against these): which = 0 VissmFlowDesc, 1 VissmFlowParams, 2 VissmFlowGrads, 3 VissmElboData, 4 VissmColStatDesc, 5 VissmSimDesc; out = {size,

@@ -7,6 +7,8 @@
 // step (colstat_math.hpp) are checked against the floats' own order and std::nth_element;
 // the forecast's Euler-Maruyama steps (sim_math.hpp) are run for each model against a double restatement, over a
 // dying LV row and over H = 0 and 1;
+// the base noise's Philox4x32-10 (rng_math.hpp) is run on the Random123 known-answer vectors and, against a
+// restatement with separate high and low multiplies, on a few thousand counters; u01 on the ends of its range;
 // any sanitizer report aborts the run (-fno-sanitize-recover=all).
 // Exit 0 = all checks passed.  Not part of the product path.
 #include <cmath>
@@ -29,6 +31,8 @@ void vissm_host_col_narrow(const int32_t* hist, int32_t* rank_left, uint32_t* pr
 void hc_sim_step(int model, const float* x, const float* th, float dt, const float* n, float* out);
 void hc_sim_path(int model, const float* x_start, const float* th, float dt, float obs_std, int H,
                  const float* normals, float* x_out, float* y_out, float* x_end);
+void hc_philox(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
+float hc_u01(uint32_t w);
 }
 
 namespace {
@@ -292,6 +296,59 @@ int check_sim_dead() {
   return bad;
 }
 
+// Philox4x32-10 round by round from the paper: mulhi / mullo apart, the key bumped after each of the first nine rounds
+void philox_ref(const uint32_t c_in[4], const uint32_t k_in[2], uint32_t out[4]) {
+  uint32_t c[4] = {c_in[0], c_in[1], c_in[2], c_in[3]}, k[2] = {k_in[0], k_in[1]};
+  for (int r = 0; r < 10; ++r) {
+    if (r > 0) { k[0] += 0x9E3779B9u; k[1] += 0xBB67AE85u; }
+    const uint64_t p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];
+    const uint32_t n[4] = {static_cast<uint32_t>(p1 >> 32) ^ c[1] ^ k[0], static_cast<uint32_t>(p1 & 0xFFFFFFFFull),
+                           static_cast<uint32_t>(p0 >> 32) ^ c[3] ^ k[1], static_cast<uint32_t>(p0 & 0xFFFFFFFFull)};
+    for (int i = 0; i < 4; ++i) c[i] = n[i];
+  }
+  for (int i = 0; i < 4; ++i) out[i] = c[i];
+}
+
+int check_philox() {
+  struct Kat { uint32_t c[4], k[2], want[4]; };
+  const Kat kats[3] = {
+      {{0u, 0u, 0u, 0u}, {0u, 0u}, {0x6627e8d5u, 0xe169c58du, 0xbc57ac4cu, 0x9b00dbd8u}},
+      {{0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu}, {0xffffffffu, 0xffffffffu},
+       {0x408f276du, 0x41c83b0eu, 0xa20bc7c6u, 0x6d5451fdu}},
+      {{0x243f6a88u, 0x85a308d3u, 0x13198a2eu, 0x03707344u}, {0xa4093822u, 0x299f31d0u},
+       {0xd16cfe09u, 0x94fdccebu, 0x5001e420u, 0x24126ea1u}}};
+  int bad = 0;
+  for (const Kat& t : kats) {
+    uint32_t got[4] = {0u, 0u, 0u, 0u};
+    hc_philox(t.c, t.k, got);
+    if (std::memcmp(got, t.want, sizeof got) != 0) {
+      std::printf("philox known answer: %08x %08x %08x %08x, want %08x %08x %08x %08x\n", got[0], got[1], got[2],
+                  got[3], t.want[0], t.want[1], t.want[2], t.want[3]);
+      ++bad;
+    }
+  }
+  // random counters and keys, then the kernels' layout (group, 0, lo(row), hi(row)) with rows around 2^32
+  for (int i = 0; i < 4096; ++i) {
+    uint32_t c[4], k[2], got[4], ref[4];
+    for (uint32_t& v : c) v = static_cast<uint32_t>(uniform(0.0, 4294967296.0));
+    for (uint32_t& v : k) v = static_cast<uint32_t>(uniform(0.0, 4294967296.0));
+    if (i >= 2048) {
+      const uint64_t row = 0xFFFFFFFFull - 1024 + static_cast<uint64_t>(i - 2048);
+      c[0] = static_cast<uint32_t>(i & 255); c[1] = 0u;
+      c[2] = static_cast<uint32_t>(row); c[3] = static_cast<uint32_t>(row >> 32);
+    }
+    hc_philox(c, k, got);
+    philox_ref(c, k, ref);
+    if (std::memcmp(got, ref, sizeof got) != 0) { std::printf("philox: counter %d differs from the restatement\n", i); ++bad; }
+  }
+  for (uint32_t w : {0x00000000u, 0x000000FFu, 0x00000100u, 0xFFFFFEFFu, 0xFFFFFF00u, 0xFFFFFFFFu, 0x80000000u}) {
+    const float want = static_cast<float>((static_cast<double>(w >> 8) + 1.0) / 16777216.0);
+    const float got = hc_u01(w);
+    if (got != want || !(got > 0.f) || got > 1.f) { std::printf("u01(%08x): %.9g vs %.9g\n", w, got, want); ++bad; }
+  }
+  return bad;
+}
+
 }  // namespace
 
 int main() {
@@ -313,6 +370,7 @@ int main() {
   if (!std::isfinite(o) || std::fabs(gx + 2.f) > 1e-5f) { std::printf("obs_term: gx %g\n", gx); ++bad; }
   for (int model = 0; model < 4; ++model) bad += check_sim(model, 50);
   bad += check_sim_dead();
+  bad += check_philox();
   bad += check_colkey();
   bad += check_select();
   for (int which = 0; which < 6; ++which) {
