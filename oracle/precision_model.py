@@ -17,7 +17,9 @@ exactly the operands the HIP kernels round in a mode (flow_v5.hip; include/vissm
   wg_x    the weight-gradient products' activation operands (dW = I dZ^T reads the bf16 images)   every bf16 mode
 
 The emulation covers the one-hidden-layer AR flows (the modes' kernels: bwd2_kernel / fwd2_kernel / the fused last
-flow); the three-hidden-layer families' BN / stride-2 heads run the plain oracle.
+flow); the three-hidden-layer families' BN / stride-2 heads run the plain oracle here.  Their rounding model -- the
+same switches, BMM and realisations applied to the kernels' BN-folded operands, at either stride -- is
+tests/flow_ref.py, the per-flow reference of the kernel-level tests (tests/test_gpu_flow_abi.py).
 """
 from __future__ import annotations
 
