@@ -608,6 +608,55 @@ int vissm_sde_simulate(const VissmSimDesc* d, uint64_t seed, uint64_t row0,
                        float* x_end /* [B][S] */, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Bootstrap particle filter of the AR, LV and FHN state-space models: an estimate of log p(y | theta) per theta row
+ * and the filtering cloud, neither of which comes out of the flows.  The reference has no filter; the loop restates
+ * its transition and observation models (AR.py:168-176, lotka_volterra_partial.py:234-261, fitz_nag_NVP.py:232-255)
+ * as propagate / weight / resample.  SV is refused (VISSM_EINVAL): it has no observation model, the rule of
+ * with_obs in vissm_sde_simulate.
+ *
+ * K filters, one block and one theta row each, N particles per filter (64, 128, 256, 512 or 1024: one per lane, a
+ * power of two), H steps per call from absolute step t0.  obs, obs_bin: [S][T_total] fp32, shared by all filters and
+ * indexed by absolute step; observation t scores the state after transition t (row e - 1 of element e in
+ * vissm_elbo_fwd's alignment).  t0 + H <= T_total and (t0 + H) S < 2^31.
+ *
+ * Step t0 + t: (1) the step of vissm_sde_simulate with its death rule; particle (k, i) consumes exactly the normals
+ * that call gives row row0 + k N + i with n_stream = S (counter (j / 4, 0, row), key seed).  (2) If any coordinate of
+ * obs_bin[:, t0 + t] is non-zero, with sums over the particles of filter k (csrc/pf_math.hpp):
+ *   logw_i = sum_d bin_d log N(y_d; x_i,d, obs_std)       (coordinates with bin_d = 0 are not read)
+ *   m = max over live i of logw_i;  q_i = (uint64) trunc(exp(logw_i - m) 2^40), exp in fp32; q_i = 0 for a dead
+ *   particle (NaN state);  W = sum q_i, an exact integer < 2^50
+ *   ll_inc = m + log W - 40 ln 2 - ln N  (double);  ess = W^2 / sum q_i^2  (double, fixed order)
+ *   U = x >> 8 of philox4x32_10(ctr = (t0 + t, 1, lo32(r), hi32(r)), key = seed), r = row0 + k N
+ *   tau_j = ((j 2^24 + U) W) >> (24 + log2 N);  anc[j] = #{i : C_i <= tau_j}, C the inclusive cumulative sum of q
+ *   slot j takes the state of particle anc[j] and keeps its own Philox row.
+ * At an unobserved step ll_inc = 0, ess = N, q_trace = 0 and anc_trace = the identity.  If W = 0 at an observed step
+ * (no live particle with a non-zero weight) the filter is dead from that step on: loglik = -inf, and its cloud,
+ * state_end, ll_inc and ess are NaN.  A call whose loglik_in[k] is -inf continues a dead filter.
+ *
+ * loglik [K] double = loglik_in (NULL: 0) + the increments; ll_inc, ess [K][H]; state_end [K N][S]; optional cloud
+ * [K N][S][H], the equally weighted post-resampling particles, sample-major (what vissm_col_* summarise), staged in
+ * LDS and written as row segments of 64, 32 or (LV / FHN at N = 1024) 16 consecutive steps; optional traces for
+ * tests, NULL in production: q_trace [K][H][N] uint64, anc_trace [K][H][N] int32.  x_start [K N][S]: a start state
+ * that fails the death rule is a dead particle.  t0 > 0 with x_start = the previous call's state_end and loglik_in =
+ * its loglik continues bitwise.  No workspace, no float atomics, fixed-order double sums: two launches are bitwise
+ * equal, and filter k's bits depend on (seed, row0 + k N, theta_k, N, data) only, not on K or the block index.
+ * vissm_particle_filter_lds_bytes: the LDS one block declares (host arithmetic; 0 = bad model or N).
+ * ------------------------------------------------------------------------- */
+typedef struct {
+  int32_t model, K, N, H, t0, T_total;
+  float dt, obs_std;
+} VissmPfDesc;
+
+int32_t vissm_particle_filter_lds_bytes(int32_t model, int32_t N);
+int vissm_particle_filter(const VissmPfDesc* d, uint64_t seed, uint64_t row0,
+                          const float* theta /* [K][P] */, const float* x_start /* [K N][S] */,
+                          const float* obs /* [S][T_total] */, const float* obs_bin /* [S][T_total] */,
+                          const double* loglik_in /* [K] or NULL */, double* loglik /* [K] */,
+                          float* ll_inc /* [K][H] */, float* ess /* [K][H] */, float* state_end /* [K N][S] */,
+                          float* cloud /* [K N][S][H] or NULL */, uint64_t* q_trace /* [K][H][N] or NULL */,
+                          int32_t* anc_trace /* [K][H][N] or NULL */, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Opt-in kernel timing (for bench.py's live roofline): when enabled, the flow
  * entry points bracket their main kernel with hipEvents on the launch stream.
  * kind: VISSM_PROF_FLOW_FWD / VISSM_PROF_FLOW_BWD (flow kernels),

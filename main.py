@@ -53,6 +53,8 @@ def run(argv=None):
         model.save_summary(args.summary)   # every rank: its collectives span the ranks; rank 0 writes
     if args.forecast:
         model.save_forecast(args.forecast[1], args.forecast[0])   # every rank, as the summary
+    if args.filter:
+        model.save_filter(args.filter[2], args.filter[0], args.filter[1])   # every rank the same launches; rank 0 writes
     return model
 
 

@@ -116,6 +116,13 @@ class SimDesc(ctypes.Structure):
                 [("with_obs", _i32)])
 
 
+PF_PARTICLES = (64, 128, 256, 512, 1024)   # VissmPfDesc.N: one particle per lane, a power of two
+
+
+class PfDesc(ctypes.Structure):
+    _fields_ = ([(n, _i32) for n in ("model", "K", "N", "H", "t0", "T_total")] + [("dt", _f32), ("obs_std", _f32)])
+
+
 # exported symbol -> (restype, argtypes); tests check that every symbol of include/vissm.h is here
 SIGNATURES = {
     "vissm_last_error": (ctypes.c_char_p, []),
@@ -195,6 +202,8 @@ SIGNATURES = {
     "vissm_col_select_decode": (_i32, [ctypes.POINTER(ColStatDesc), _c_void_p, _c_void_p, _c_void_p]),
     "vissm_sde_simulate": (_i32, [ctypes.POINTER(SimDesc), _u64, _u64, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                                   _c_void_p, _c_void_p]),
+    "vissm_particle_filter_lds_bytes": (_i32, [_i32, _i32]),
+    "vissm_particle_filter": (_i32, [ctypes.POINTER(PfDesc), _u64, _u64] + [_c_void_p] * 12 + [_c_void_p]),
     "vissm_profile_enable": (None, [_i32]),
     "vissm_profile_read": (_i32, [_i32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_i64)]),
     "vissm_profile_reset": (None, []),

@@ -37,6 +37,7 @@ class VI_SSM(VISSMBase):
         super().__init__(mdef, table, theta_dist, p, pre_train, early_stopping, learn_rate, grad_clip,
                          device=device, seed=seed, precision=precision, dist=dist, log_every=log_every,
                          init_seed=init_seed)
+        self._keep_filter_data(obs, obs_bin, x0)
 
     def pretrain_step(self, batch: Batch, run: int) -> bool:
         """AR.py:201-202, 290-298: Adamax(1e-3, beta1=0.9).minimize(-obs_loss) for runs 0..500."""

@@ -135,7 +135,18 @@ def handle_opts(argv=None):
     parser.add_argument("--forecast", nargs=2, metavar=("H", "PATH"), default=None,
                         help="After training, simulate the fitted model H steps past the data on the GPU and write the "
                              "posterior-predictive forecast (mean, sd and quantile bands over time) to this .npz file")
+    parser.add_argument("--filter", nargs=3, metavar=("K", "N", "PATH"), default=None,
+                        help="After training, run K bootstrap particle filters of N particles each (64 .. 1024, a "
+                             "power of two) on the GPU, one per posterior theta sample, and write their log-evidence "
+                             "estimates and filtering bands to this .npz file")
     args = parser.parse_args(argv)
+    if args.filter is not None:
+        try:
+            args.filter = (int(args.filter[0]), int(args.filter[1]), args.filter[2])
+        except ValueError:
+            parser.error(f"--filter: K and N must be integers, got {args.filter[0]!r} {args.filter[1]!r}")
+        if args.filter[0] < 1 or args.filter[1] not in (64, 128, 256, 512, 1024):
+            parser.error("--filter: K >= 1 and N one of 64, 128, 256, 512, 1024 expected")
     if args.forecast is not None:
         try:
             args.forecast = (int(args.forecast[0]), args.forecast[1])

@@ -1,7 +1,8 @@
 // Host (CPU) build of elbo_math.hpp so the CPU test-suite can check the
 // hand-derived transition gradients against the oracle's autograd without a GPU,
 // of sim_math.hpp (the forecast kernel's Euler-Maruyama steps) against a float64 restatement,
-// and of rng_math.hpp (Philox4x32-10 and u01) against tests/philox_ref.py.
+// of rng_math.hpp (Philox4x32-10 and u01) against tests/philox_ref.py,
+// and of pf_math.hpp (the particle filter's integer weights and resampling) against Python big-int arithmetic.
 // Not part of the product path: libvissm_hostcheck.so is loaded only by tests/.
 #include <cstddef>
 
@@ -10,6 +11,7 @@
 #include "colstat_math.hpp"
 #include "sim_math.hpp"
 #include "rng_math.hpp"
+#include "pf_math.hpp"
 
 extern "C" {
 
@@ -65,8 +67,22 @@ void hc_philox(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
 
 float hc_u01(uint32_t w) { return vissm::u01(w); }
 
+// The particle filter's integer half (pf_math.hpp: the code particle_filter_kernel runs): the quantised weight, one
+// resampling threshold, the resampling integer, and systematic resampling run serially -- anc [n], C [n] the
+// inclusive cumulative sum; returns W (0: anc untouched)
+uint64_t hc_pf_quantise(float logw, float m, int alive) { return vissm::pf::quantise(logw, m, alive != 0); }
+uint64_t hc_pf_threshold(uint32_t j, uint32_t U, uint64_t W, int log2n) { return vissm::pf::threshold(j, U, W, log2n); }
+uint32_t hc_pf_resample_u(uint64_t seed, uint32_t t, uint64_t r) { return vissm::pf::resample_u(seed, t, r); }
+uint64_t hc_pf_resample(const uint64_t* q, int n, uint32_t U, int32_t* anc, uint64_t* C) {
+  return vissm::pf::resample(q, n, U, anc, C);
+}
+float hc_pf_logw(int model, const float* x, const float* y, const float* bin, float sd) {
+  return vissm::pf::obs_logw(VISSM_MODEL_S(model), x, y, bin, sd);
+}
+double hc_pf_ll_increment(float m, uint64_t W, int n) { return vissm::pf::ll_increment(m, W, n); }
+
 // the C ABI's struct layouts as the C compiler sees them (the ctypes mirrors in viforssms_amd/_lib.py are
-// checked against these): which = 0 VissmFlowDesc, 1 VissmFlowParams, 2 VissmFlowGrads, 3 VissmElboData, 4 VissmColStatDesc, 5 VissmSimDesc; out = {size,
+// checked against these): which = 0 VissmFlowDesc, 1 VissmFlowParams, 2 VissmFlowGrads, 3 VissmElboData, 4 VissmColStatDesc, 5 VissmSimDesc, 6 VissmPfDesc; out = {size,
 // offset of the last field}
 void vissm_host_abi_layout(int which, size_t* out) {
   switch (which) {
@@ -75,6 +91,7 @@ void vissm_host_abi_layout(int which, size_t* out) {
     case 2: out[0] = sizeof(VissmFlowGrads); out[1] = offsetof(VissmFlowGrads, b_head); break;
     case 5: out[0] = sizeof(VissmSimDesc); out[1] = offsetof(VissmSimDesc, with_obs); break;
     case 4: out[0] = sizeof(VissmColStatDesc); out[1] = offsetof(VissmColStatDesc, n_ranks); break;
+    case 6: out[0] = sizeof(VissmPfDesc); out[1] = offsetof(VissmPfDesc, obs_std); break;
     default: out[0] = sizeof(VissmElboData); out[1] = offsetof(VissmElboData, obs_stride); break;
   }
 }

@@ -9,6 +9,8 @@
 // dying LV row and over H = 0 and 1;
 // the base noise's Philox4x32-10 (rng_math.hpp) is run on the Random123 known-answer vectors and, against a
 // restatement with separate high and low multiplies, on a few thousand counters; u01 on the ends of its range;
+// the particle filter's quantised weights, thresholds and serial systematic resampling (pf_math.hpp) on their edge
+// cases against a 128-bit restatement;
 // any sanitizer report aborts the run (-fno-sanitize-recover=all).
 // Exit 0 = all checks passed.  Not part of the product path.
 #include <cmath>
@@ -33,6 +35,11 @@ void hc_sim_path(int model, const float* x_start, const float* th, float dt, flo
                  const float* normals, float* x_out, float* y_out, float* x_end);
 void hc_philox(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 float hc_u01(uint32_t w);
+uint64_t hc_pf_quantise(float logw, float m, int alive);
+uint64_t hc_pf_threshold(uint32_t j, uint32_t U, uint64_t W, int log2n);
+uint32_t hc_pf_resample_u(uint64_t seed, uint32_t t, uint64_t r);
+uint64_t hc_pf_resample(const uint64_t* q, int n, uint32_t U, int32_t* anc, uint64_t* C);
+double hc_pf_ll_increment(float m, uint64_t W, int n);
 }
 
 namespace {
@@ -349,6 +356,72 @@ int check_philox() {
   return bad;
 }
 
+// The particle filter's integer half (pf_math.hpp).  Thresholds against a 128-bit restatement; systematic resampling
+// against a linear count of the cumulative sums, over U = 0 and 2^24 - 1, N = 64 and 1024, a single survivor with
+// W = 2^40, W one below 2^50 (every weight 2^40 but one), runs of zero weights, and weights whose cumulative sums the
+// thresholds hit exactly (equal weights at U = 0: tau_j = j q = C_{j-1}); quantise on the ends of its range.
+int check_pf() {
+  int bad = 0;
+  const uint32_t Umax = (1u << 24) - 1u;
+  for (int n : {64, 1024}) {
+    int l = 0;
+    while ((1 << l) < n) ++l;
+    std::vector<std::vector<uint64_t>> cases;
+    std::vector<uint64_t> q(n, 0);
+    q[n / 3] = 1ull << 40;  // a single survivor
+    cases.push_back(q);
+    std::fill(q.begin(), q.end(), 1ull << 40);  // W = N 2^40 (2^50 at N = 1024), every tau on a C_i at U = 0
+    cases.push_back(q);
+    q[n - 1] -= 1;  // one below
+    cases.push_back(q);
+    for (int i = 0; i < n; ++i) q[i] = (i / 7) % 2 ? 0ull : static_cast<uint64_t>(uniform(0.0, 1099511627776.0));
+    q[5] = 1ull << 40;  // runs of zeros
+    cases.push_back(q);
+    for (int i = 0; i < n; ++i) q[i] = i < n - 3 ? 0ull : 1ull;  // W = 3, zeros first
+    cases.push_back(q);
+    for (int i = 0; i < n; ++i) q[i] = static_cast<uint64_t>(std::exp(uniform(-30.0, 0.0)) * 1099511627776.0);
+    q[0] = 1ull << 40;
+    cases.push_back(q);
+    for (const auto& qc : cases)
+      for (uint32_t U : {0u, 1u, Umax / 2u, Umax}) {
+        std::vector<int32_t> anc(n, -1);
+        std::vector<uint64_t> C(n, 0);
+        const uint64_t W = hc_pf_resample(qc.data(), n, U, anc.data(), C.data());
+        uint64_t sum = 0;
+        for (int i = 0; i < n; ++i) {
+          sum += qc[i];
+          if (C[i] != sum) { std::printf("pf: cumulative sum %d\n", i); ++bad; }
+        }
+        if (W != sum) { std::printf("pf: W\n"); ++bad; }
+        for (int j = 0; j < n; ++j) {
+          const unsigned __int128 a = (static_cast<unsigned __int128>(j) << 24) + U;
+          const uint64_t tau = static_cast<uint64_t>((a * W) >> (24 + l));
+          if (hc_pf_threshold(static_cast<uint32_t>(j), U, W, l) != tau) { std::printf("pf: threshold %d\n", j); ++bad; }
+          int want = 0;
+          for (int i = 0; i < n; ++i) want += C[i] <= tau;
+          if (anc[j] != want || want >= n || qc[want] == 0) {
+            std::printf("pf: n %d U %u slot %d: ancestor %d, want %d\n", n, U, j, anc[j], want);
+            ++bad;
+          }
+        }
+      }
+    std::vector<uint64_t> zero(n, 0), C(n, 0);
+    std::vector<int32_t> anc(n, -7);
+    if (hc_pf_resample(zero.data(), n, 5u, anc.data(), C.data()) != 0 || anc[0] != -7) { std::printf("pf: W = 0\n"); ++bad; }
+  }
+  if (hc_pf_quantise(-3.f, -3.f, 1) != (1ull << 40)) { std::printf("pf: quantise at the maximum\n"); ++bad; }
+  if (hc_pf_quantise(-3.f, -3.f, 0) != 0) { std::printf("pf: quantise of a dead particle\n"); ++bad; }
+  if (hc_pf_quantise(-200.f, 0.f, 1) != 0) { std::printf("pf: quantise underflow\n"); ++bad; }
+  if (hc_pf_quantise(-INFINITY, -INFINITY, 1) != 0) { std::printf("pf: quantise without a finite weight\n"); ++bad; }
+  if (hc_pf_quantise(-INFINITY, 0.f, 1) != 0) { std::printf("pf: quantise of -inf\n"); ++bad; }
+  const uint64_t half = hc_pf_quantise(-0.6931472f, 0.f, 1);
+  if (half < (1ull << 39) - (1ull << 18) || half > (1ull << 39) + (1ull << 18)) { std::printf("pf: quantise(ln 1/2)\n"); ++bad; }
+  if (hc_pf_resample_u(1u, 2u, 3u) >= (1u << 24)) { std::printf("pf: U range\n"); ++bad; }
+  const double li = hc_pf_ll_increment(-1.5f, 1ull << 40, 64);
+  if (std::fabs(li - (-1.5 - std::log(64.0))) > 1e-12) { std::printf("pf: ll_increment %g\n", li); ++bad; }
+  return bad;
+}
+
 }  // namespace
 
 int main() {
@@ -371,9 +444,10 @@ int main() {
   for (int model = 0; model < 4; ++model) bad += check_sim(model, 50);
   bad += check_sim_dead();
   bad += check_philox();
+  bad += check_pf();
   bad += check_colkey();
   bad += check_select();
-  for (int which = 0; which < 6; ++which) {
+  for (int which = 0; which < 7; ++which) {
     size_t out[2] = {0, 0};
     vissm_host_abi_layout(which, out);
     if (out[0] == 0 || out[1] >= out[0]) { std::printf("abi layout %d: %zu %zu\n", which, out[0], out[1]); ++bad; }

@@ -40,6 +40,7 @@ class VI_SSM(VISSMBase):
         self.pre_train_count = 0
         super().__init__(mdef, table, theta_dist, p, pre_train, 1e99, learn_rate, grad_clip, device=device,
                          seed=seed, precision=precision, dist=dist, log_every=log_every, init_seed=init_seed)
+        self._keep_filter_data(obs, obs_bin, x0)
         self._frozen = None
         if not train_paths:
             mask = torch.ones_like(self.store.grad)

@@ -37,6 +37,7 @@ class VI_SSM(VISSMBase):
         self.pre_train_count = 0
         super().__init__(mdef, table, theta_dist, p, pre_train, 1e99, learn_rate, grad_clip, device=device,
                          seed=seed, precision=precision, dist=dist, log_every=log_every, init_seed=init_seed)
+        self._keep_filter_data(obs, obs_bin, x0)
 
     def target_len(self) -> int:
         return self.target_dims

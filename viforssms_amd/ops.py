@@ -963,3 +963,85 @@ def sde_simulate(model_id: int, theta: torch.Tensor, x_start: torch.Tensor, H: i
                                          ctypes.c_uint64(int(row0)), ptr(theta), ptr(x_start), ptr(x), ptr(y),
                                          ptr(x_end), _lib.stream_handle(dev)), "vissm_sde_simulate")
     return x, y, x_end
+
+
+# ---------------------------------------------------------------------------------------
+# bootstrap particle filter (log-evidence and filtering bands)
+# ---------------------------------------------------------------------------------------
+@dataclass
+class ParticleFilterResult:
+    loglik: torch.Tensor                 # [K] float64: loglik_in + the increments (-inf: a dead filter)
+    ll_inc: torch.Tensor                 # [K, H] fp32, 0 at unobserved steps
+    ess: torch.Tensor                    # [K, H] fp32, N at unobserved steps
+    state_end: torch.Tensor              # [K N, S]
+    cloud: Optional[torch.Tensor]        # [K N, S, H] post-resampling particles, or None
+    q_trace: Optional[torch.Tensor]      # [K, H, N] int64 (the kernel's uint64 weights, below 2^41), or None
+    anc_trace: Optional[torch.Tensor]    # [K, H, N] int32, or None
+
+
+def particle_filter(model_id: int, theta: torch.Tensor, x_start: torch.Tensor, obs: torch.Tensor,
+                    obs_bin: torch.Tensor, dt: float, obs_std: float, N: int, seed: int, row0: int, t0: int = 0,
+                    loglik_in: Optional[torch.Tensor] = None, cloud: bool = True, trace: bool = False,
+                    H: Optional[int] = None) -> ParticleFilterResult:
+    """K bootstrap particle filters of N particles each, one per row of theta [K, P] (raw, as the ELBO takes it), over
+    steps t0 .. t0 + H - 1 of obs / obs_bin [S, T_total] (H = T_total - t0 by default); vissm_particle_filter: one
+    block per filter, one particle per lane, integer systematic resampling.  x_start: [K N, S], or [S] for every
+    particle.  Observation t scores the state after transition t.  Particle (k, i) consumes the normals
+    sde_simulate gives row row0 + k N + i under the same seed, so with obs_bin = 0 the cloud is that call's x.  A
+    call with t0 > 0, x_start = the previous call's state_end and loglik_in = its loglik continues bitwise.  AR, LV
+    and FHN; SV has no observation model and is refused."""
+    if model_id not in _lib.MODEL_S:
+        raise _lib.VissmError(f"particle_filter: unknown model {model_id}")
+    if model_id == _lib.MODEL_SV:
+        raise _lib.VissmError("particle_filter: no observation model for SV (its first coordinate is the observed "
+                              "series)")
+    S, P = _lib.MODEL_S[model_id], _lib.MODEL_P[model_id]
+    N = int(N)
+    if N not in _lib.PF_PARTICLES:
+        raise _lib.VissmError(f"particle_filter: N={N} particles, one of {_lib.PF_PARTICLES} expected")
+    _require_gpu(theta, x_start, obs, obs_bin)
+    for name, t in (("theta", theta), ("x_start", x_start), ("obs", obs), ("obs_bin", obs_bin)):
+        if t.dtype != torch.float32:
+            raise _lib.VissmError(f"particle_filter: fp32 {name} expected, got {t.dtype}")
+    if theta.dim() != 2 or theta.shape[1] != P:
+        raise _lib.VissmError(f"particle_filter: theta [K, {P}] expected, got {tuple(theta.shape)}")
+    K = theta.shape[0]
+    if K * N >= 2 ** 31:
+        raise _lib.VissmError(f"particle_filter: K N = {K} * {N} reaches 2^31")
+    if x_start.dim() == 1 and x_start.shape[0] == S:
+        x_start = x_start.unsqueeze(0).expand(K * N, S).contiguous()
+    if x_start.dim() != 2 or tuple(x_start.shape) != (K * N, S):
+        raise _lib.VissmError(f"particle_filter: x_start [{K * N}, {S}] or [{S}] expected, got {tuple(x_start.shape)}")
+    if obs.dim() != 2 or obs.shape[0] != S or obs_bin.shape != obs.shape:
+        raise _lib.VissmError(f"particle_filter: obs and obs_bin [{S}, T] expected, got {tuple(obs.shape)} and "
+                              f"{tuple(obs_bin.shape)}")
+    dev = theta.device
+    if any(t.device != dev for t in (x_start, obs, obs_bin)):
+        raise _lib.VissmError("particle_filter: all tensors on one device expected")
+    T_total, t0 = obs.shape[1], int(t0)
+    H = T_total - t0 if H is None else int(H)
+    if H < 0 or t0 < 0 or t0 + H > T_total or (t0 + H) * S >= 2 ** 31:
+        raise _lib.VissmError(f"particle_filter: bad horizon H={H} t0={t0} for {T_total} observations "
+                              f"((t0 + H) * {S} must stay below 2^31)")
+    if not 0 <= int(row0) < 2 ** 64:
+        raise _lib.VissmError(f"particle_filter: row0={row0} outside [0, 2^64)")
+    if loglik_in is not None:
+        if not loglik_in.is_cuda or loglik_in.device != dev or loglik_in.dtype != torch.float64 or \
+                tuple(loglik_in.shape) != (K,) or not loglik_in.is_contiguous():
+            raise _lib.VissmError(f"particle_filter: loglik_in: a contiguous float64 GPU tensor [{K}] expected")
+    loglik = torch.empty(K, dtype=torch.float64, device=dev)
+    ll_inc = torch.empty(K, H, dtype=torch.float32, device=dev)
+    ess = torch.empty(K, H, dtype=torch.float32, device=dev)
+    state_end = torch.empty(K * N, S, dtype=torch.float32, device=dev)
+    cl = torch.empty(K * N, S, H, dtype=torch.float32, device=dev) if cloud else None
+    qt = torch.empty(K, H, N, dtype=torch.int64, device=dev) if trace else None
+    at = torch.empty(K, H, N, dtype=torch.int32, device=dev) if trace else None
+    if K == 0:
+        return ParticleFilterResult(loglik, ll_inc, ess, state_end, cl, qt, at)
+    d = _lib.PfDesc(model_id, K, N, H, t0, T_total, float(dt), float(obs_std))
+    check(_lib.load().vissm_particle_filter(ctypes.byref(d), ctypes.c_uint64(seed & (2 ** 64 - 1)),
+                                            ctypes.c_uint64(int(row0)), ptr(theta), ptr(x_start), ptr(obs),
+                                            ptr(obs_bin), ptr(loglik_in), ptr(loglik), ptr(ll_inc), ptr(ess),
+                                            ptr(state_end), ptr(cl), ptr(qt), ptr(at), _lib.stream_handle(dev)),
+          "vissm_particle_filter")
+    return ParticleFilterResult(loglik, ll_inc, ess, state_end, cl, qt, at)

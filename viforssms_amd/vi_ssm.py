@@ -23,6 +23,8 @@ from .summary import DEFAULT_PROBS, _check_probs, column_summary
 # Philox key of the forecast's normals: the engine's seed xor this (Engine.draw keys eps by the seed itself and the
 # q(theta) base draw by seed ^ 0x5DEECE66D)
 FORECAST_SEED_XOR = 0xF02ECA57
+# Philox key of the particle filter's normals and resampling integers: a fourth key next to the forecast's
+FILTER_SEED_XOR = 0xF117E2ED
 # device bytes one forecast launch may write per output ([B, S, chunk] fp32): the default chunk is the largest
 # multiple of the kernel's tile under it
 FORECAST_CHUNK_BYTES = 256 << 20
@@ -107,6 +109,7 @@ class VISSMBase:
         self._opt_pre: List[AdamaxSlots] = []
         self.last: Dict[str, float] = {}
         self.global_step = 0
+        self.filter_data = None   # (obs, obs_bin, x0) of particle_filter(): AR, LV and FHN keep them (_keep_filter_data)
 
     # ------------------------------------------------------------------ graph
     def build_flow(self):
@@ -685,3 +688,97 @@ class VISSMBase:
             with open(PATH, "wb") as f:
                 np.savez(f, **res)
         return res
+
+    # ------------------------------------------------------------------ particle filter
+    def filter_chunk(self, n_theta: int, n_particles: int) -> int:
+        """Steps per launch of particle_filter() by default: the [K N, S, chunk] fp32 cloud stays under
+        FORECAST_CHUNK_BYTES (a multiple of the forecast tile, at least one)."""
+        steps = FORECAST_CHUNK_BYTES // (4 * _lib.MODEL_S[self.mdef.model_id] * max(n_theta * n_particles, 1))
+        return max(_lib.SIM_TILE, steps // _lib.SIM_TILE * _lib.SIM_TILE)
+
+    @torch.no_grad()
+    def particle_filter(self, n_theta: int = 64, n_particles: int = 1024, probs=DEFAULT_PROBS,
+                        chunk: Optional[int] = None) -> Dict[str, np.ndarray]:
+        """A check of the fitted posterior that does not come out of the flows: K = n_theta bootstrap particle filters
+        of N = n_particles particles each (ops.particle_filter), one per theta sample, over the model's observations
+        from its x0.  theta = global samples 0 .. K - 1 of the first window's draw posterior_summary uses (same
+        start, same step): rank 0's first rows, broadcast, so K <= p_local.  Every rank runs the identical
+        deterministic launches and holds the same result; nothing is sharded.
+
+        filter/loglik [K] float64 estimates log p(y | theta_k) (-inf: every particle died); filter/theta [K, P] the
+        raw theta rows; filter/ll_inc and filter/ess [K, T] the per-step increments (0 where nothing is observed) and
+        effective sample sizes (N there); filter/{mean, sd, n_valid} [S, T] and filter/quantiles [Q, S, T] summarise
+        the K N equally weighted post-resampling particles of each step (summary.column_summary): the theta_k are iid
+        from q(theta), so this is the filtering distribution averaged over q(theta).  T = min(target_len(), the
+        observations' length).  Philox key seed ^ FILTER_SEED_XOR, rows global_step K N + k N + i; `chunk` steps per
+        launch (default filter_chunk()), chained through the end state and the running log-likelihood, change
+        nothing.  SV has no observation model: ValueError."""
+        from . import ops
+        md = self.mdef
+        if md.model_id == _lib.MODEL_SV or getattr(self, "filter_data", None) is None:
+            raise ValueError("particle_filter: SV has no observation model (its first coordinate is the observed "
+                             "series)")
+        K, N = int(n_theta), int(n_particles)
+        if N not in _lib.PF_PARTICLES:
+            raise ValueError(f"particle_filter: n_particles={N}, one of {_lib.PF_PARTICLES} expected")
+        if not 1 <= K <= self.p_local:
+            raise ValueError(f"particle_filter: n_theta={K} outside 1 .. p_local = {self.p_local}")
+        p = _check_probs(probs)
+        chunk = self.filter_chunk(K, N) if chunk is None else int(chunk)
+        if chunk < 1:
+            raise ValueError(f"particle_filter chunk {chunk} < 1")
+        dev = self.engine.device
+        S, Q = _lib.MODEL_S[md.model_id], p.size
+        obs_h, bin_h, x0_h = self.filter_data
+        T = min(int(self.target_len()), obs_h.shape[1])
+        obs = torch.as_tensor(np.ascontiguousarray(obs_h[:, :T]), device=dev)
+        obs_bin = torch.as_tensor(np.ascontiguousarray(bin_h[:, :T]), device=dev)
+        x0 = torch.as_tensor(x0_h, device=dev)
+        _, theta = self.sample_paths_theta(np.tile(0, self.p_local), step=self.global_step)
+        th = theta.detach().float()[:K].contiguous()
+        if self.dist.world > 1:
+            import torch.distributed as dist
+            dist.broadcast(th, src=dist.get_global_rank(self.dist.group, 0) if self.dist.group is not None else 0,
+                           group=self.dist.group)
+        seed = self.engine.seed ^ FILTER_SEED_XOR
+        row0 = self.global_step * K * N
+        state, ll = x0, None
+        incs, esss, parts = [], [], []
+        for t0 in range(0, T, chunk):
+            m = min(chunk, T - t0)
+            r = ops.particle_filter(md.model_id, th, state, obs, obs_bin, md.dt, md.obs_std, N, seed, row0, t0=t0,
+                                    loglik_in=ll, cloud=True, H=m)
+            state, ll = r.state_end, r.loglik
+            incs.append(r.ll_inc)
+            esss.append(r.ess)
+            parts.append((m, column_summary(r.cloud.view(K * N, S * m), probs, None)))
+        res: Dict[str, np.ndarray] = {"probs": p, "filter/theta": th.cpu().numpy()}
+        res["filter/loglik"] = ll.cpu().numpy() if ll is not None else np.zeros(K)
+        res["filter/ll_inc"] = torch.cat(incs + [torch.zeros(K, 0, device=dev)], 1).cpu().numpy()
+        res["filter/ess"] = torch.cat(esss + [torch.zeros(K, 0, device=dev)], 1).cpu().numpy()
+        for k, dt_ in (("mean", np.float64), ("sd", np.float64), ("n_valid", np.int64)):
+            res[f"filter/{k}"] = np.concatenate([s[k].reshape(S, m) for m, s in parts] +
+                                                [np.zeros((S, 0), dtype=dt_)], axis=1)
+        res["filter/quantiles"] = np.concatenate([s["quantiles"].reshape(Q, S, m) for m, s in parts] +
+                                                 [np.zeros((Q, S, 0))], axis=2)
+        return res
+
+    def save_filter(self, PATH: str, n_theta: int = 64, n_particles: int = 1024, probs=DEFAULT_PROBS,
+                    chunk: Optional[int] = None) -> Dict[str, np.ndarray]:
+        """particle_filter written as one .npz by rank 0 (every rank computes the same result)."""
+        res = self.particle_filter(n_theta, n_particles, probs, chunk)
+        if self.dist.rank == 0:
+            d = os.path.dirname(PATH)
+            if d:
+                os.makedirs(d, exist_ok=True)
+            with open(PATH, "wb") as f:
+                np.savez(f, **res)
+        return res
+
+    def _keep_filter_data(self, obs, obs_bin, x0):
+        """The raw constructor arguments the particle filter reads (the feature tables are built from copies):
+        obs, obs_bin as [S, T] fp32, x0 as [S] fp32."""
+        S = _lib.MODEL_S[self.mdef.model_id]
+        self.filter_data = (np.asarray(obs, dtype=np.float32).reshape(S, -1),
+                            np.asarray(obs_bin, dtype=np.float32).reshape(S, -1),
+                            np.asarray(x0, dtype=np.float32).reshape(S))
