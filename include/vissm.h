@@ -657,6 +657,54 @@ int vissm_particle_filter(const VissmPfDesc* d, uint64_t seed, uint64_t row0,
                           int32_t* anc_trace /* [K][H][N] or NULL */, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Particle smoother: forward filtering, backward simulation (FFBSi) over the cloud vissm_particle_filter wrote.  The
+ * filter's bands are filtering distributions p(x_t | y_1:t, theta); the trajectories drawn here are samples of the
+ * smoothing distribution p(x_1:T | y_1:T, theta), the law the variational posterior over the latent path approximates.
+ * The reference has no smoother; the backward weights restate its transition models (AR.py:172-176,
+ * lotka_volterra_partial.py:244-261, fitz_nag_NVP.py:243-255).  SV is refused (VISSM_EINVAL), as in the filter.
+ *
+ * K filters of N particles (the filter's sizes), M trajectories per filter (a power of two, 64 <= M <= N), H steps per
+ * call; t0 is the absolute step of column 0 and enters the Philox counter only.  cloud [K N][S][H] holds the equally
+ * weighted post-resampling particles of every step, so the backward weights are the transition densities alone.
+ * Trajectory (k, j) walks t from H - 1 down; with xt its state at t + 1 (x_next[k M + j] for t = H - 1) and sums over
+ * the particles i of filter k at step t (csrc/ps_math.hpp):
+ *   logw_i = log p(xt | x_i, theta_k) in fp32, the value the ELBO's transition term has, less a constant of theta
+ *   m = max over live i of logw_i;  q_i = (uint64) trunc(exp(logw_i - m) 2^40), exp in fp32; q_i = 0 for a dead
+ *   particle (not finite; for LV a coordinate <= 0);  W = sum q_i, an exact integer <= 2^50
+ *   U = x of philox4x32_10(ctr = (t0 + t, 2, lo32(r), hi32(r)), key = seed), r = row0 + k N + j, all 32 bits
+ *   tau = (U W) >> 32;  idx = #{i : C_i <= tau}, C the inclusive cumulative sum of q in particle order
+ *   paths[k M + j][:][t] = cloud[k N + idx][:][t], bit for bit.
+ * (The normals' counters carry 0 in their second word and the filter's resampling 1: the three streams never meet.)
+ * Terminal rule: with x_next = NULL, logw_i = 0 for every live particle at t = H - 1, a uniform draw over the live
+ * ones.  If W = 0 -- no live particle, or a NaN target -- the trajectory is the canonical quiet NaN at that step and
+ * idx = -1; a NaN target gives W = 0 at the step before it, so NaN propagates backward, and a filter that died at any
+ * step (its cloud is NaN from there on) has all-NaN trajectories.
+ *
+ * paths [K M][S][H] sample-major (what vissm_col_* summarise); x_first [K M][S] = paths at step 0, the x_next of the
+ * call over the H' steps before (its t0 smaller by H'): chained calls equal one call bitwise.  Optional idx [K M][H]
+ * and, for tests, q_trace [K][H][M][N] uint64.  A block owns 64 trajectories of one filter, one per lane, grid
+ * (M / 64, K); its min(4, N / 64) waves share out the particles.  The cloud is staged in LDS in tiles of 32, 16, 8 or 4
+ * steps and read as row segments of that many consecutive steps, the outputs leave the same way.  No workspace, no
+ * atomics; the maximum is exact in any order, the sums are integers and the selection is defined in particle order:
+ * two launches are bitwise equal, and trajectory (k, j) depends on (seed, row0 + k N + j, theta_k, filter k's cloud,
+ * x_next[k M + j]) only, not on K or the launch geometry.  K <= 65535, H >= 1, t0 + H < 2^31.
+ * vissm_particle_smooth_lds_bytes: the LDS one block declares (host arithmetic; 0 = bad model, N or M).
+ * ------------------------------------------------------------------------- */
+typedef struct {
+  int32_t model, K, N, M, H, t0;
+  float dt;
+} VissmPsDesc;
+
+int32_t vissm_particle_smooth_lds_bytes(int32_t model, int32_t N, int32_t M);
+int vissm_particle_smooth(const VissmPsDesc* d, uint64_t seed, uint64_t row0,
+                          const float* theta /* [K][P] */, const float* cloud /* [K N][S][H], the filter's layout */,
+                          const float* x_next /* [K M][S] or NULL: the target of step H - 1 */,
+                          float* paths /* [K M][S][H] sample-major */,
+                          float* x_first /* [K M][S]: paths at step 0, the next (earlier) call's x_next */,
+                          int32_t* idx /* [K M][H] or NULL: the chosen particle, -1 where NaN */,
+                          uint64_t* q_trace /* [K][H][M][N] or NULL: tests only */, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Opt-in kernel timing (for bench.py's live roofline): when enabled, the flow
  * entry points bracket their main kernel with hipEvents on the launch stream.
  * kind: VISSM_PROF_FLOW_FWD / VISSM_PROF_FLOW_BWD (flow kernels),

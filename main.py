@@ -55,6 +55,8 @@ def run(argv=None):
         model.save_forecast(args.forecast[1], args.forecast[0])   # every rank, as the summary
     if args.filter:
         model.save_filter(args.filter[2], args.filter[0], args.filter[1])   # every rank the same launches; rank 0 writes
+    if args.smooth:
+        model.save_smoother(args.smooth[3], args.smooth[0], args.smooth[1], args.smooth[2])   # as the filter
     return model
 
 

@@ -123,6 +123,13 @@ class PfDesc(ctypes.Structure):
     _fields_ = ([(n, _i32) for n in ("model", "K", "N", "H", "t0", "T_total")] + [("dt", _f32), ("obs_std", _f32)])
 
 
+PS_MIN_PATHS = 64   # VissmPsDesc.M: trajectories per filter, a power of two in 64 .. N (one per lane of a wave)
+
+
+class PsDesc(ctypes.Structure):
+    _fields_ = [(n, _i32) for n in ("model", "K", "N", "M", "H", "t0")] + [("dt", _f32)]
+
+
 # exported symbol -> (restype, argtypes); tests check that every symbol of include/vissm.h is here
 SIGNATURES = {
     "vissm_last_error": (ctypes.c_char_p, []),
@@ -204,6 +211,8 @@ SIGNATURES = {
                                   _c_void_p, _c_void_p]),
     "vissm_particle_filter_lds_bytes": (_i32, [_i32, _i32]),
     "vissm_particle_filter": (_i32, [ctypes.POINTER(PfDesc), _u64, _u64] + [_c_void_p] * 12 + [_c_void_p]),
+    "vissm_particle_smooth_lds_bytes": (_i32, [_i32, _i32, _i32]),
+    "vissm_particle_smooth": (_i32, [ctypes.POINTER(PsDesc), _u64, _u64] + [_c_void_p] * 7 + [_c_void_p]),
     "vissm_profile_enable": (None, [_i32]),
     "vissm_profile_read": (_i32, [_i32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_i64)]),
     "vissm_profile_reset": (None, []),

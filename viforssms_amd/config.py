@@ -139,7 +139,19 @@ def handle_opts(argv=None):
                         help="After training, run K bootstrap particle filters of N particles each (64 .. 1024, a "
                              "power of two) on the GPU, one per posterior theta sample, and write their log-evidence "
                              "estimates and filtering bands to this .npz file")
+    parser.add_argument("--smooth", nargs=4, metavar=("K", "N", "M", "PATH"), default=None,
+                        help="After training, run the K particle filters of N particles of --filter and then draw M "
+                             "smoothing trajectories per filter by backward simulation on the GPU (M a power of two, "
+                             "64 <= M <= N), and write the filter's entries and the smoothing bands to this .npz file")
     args = parser.parse_args(argv)
+    if args.smooth is not None:
+        try:
+            args.smooth = (int(args.smooth[0]), int(args.smooth[1]), int(args.smooth[2]), args.smooth[3])
+        except ValueError:
+            parser.error(f"--smooth: K, N and M must be integers, got {args.smooth[:3]!r}")
+        k_, n_, m_ = args.smooth[:3]
+        if k_ < 1 or n_ not in (64, 128, 256, 512, 1024) or not (64 <= m_ <= n_ and m_ & (m_ - 1) == 0):
+            parser.error("--smooth: K >= 1, N one of 64, 128, 256, 512, 1024 and M a power of two in 64 .. N expected")
     if args.filter is not None:
         try:
             args.filter = (int(args.filter[0]), int(args.filter[1]), args.filter[2])

@@ -2,7 +2,8 @@
 // hand-derived transition gradients against the oracle's autograd without a GPU,
 // of sim_math.hpp (the forecast kernel's Euler-Maruyama steps) against a float64 restatement,
 // of rng_math.hpp (Philox4x32-10 and u01) against tests/philox_ref.py,
-// and of pf_math.hpp (the particle filter's integer weights and resampling) against Python big-int arithmetic.
+// of pf_math.hpp (the particle filter's integer weights and resampling) against Python big-int arithmetic,
+// and of ps_math.hpp (the particle smoother's backward weights and integer selection) against float64 and big ints.
 // Not part of the product path: libvissm_hostcheck.so is loaded only by tests/.
 #include <cstddef>
 
@@ -12,6 +13,7 @@
 #include "sim_math.hpp"
 #include "rng_math.hpp"
 #include "pf_math.hpp"
+#include "ps_math.hpp"
 
 extern "C" {
 
@@ -81,8 +83,48 @@ float hc_pf_logw(int model, const float* x, const float* y, const float* bin, fl
 }
 double hc_pf_ll_increment(float m, uint64_t W, int n) { return vissm::pf::ll_increment(m, W, n); }
 
+// The particle smoother's shared math (ps_math.hpp: the code particle_smooth_kernel runs).  hc_ps_pair_logw: logw of
+// target xt from particle x (NaN for a dead one) and, in *dropped, the constant of theta it leaves out of *_trans' lp;
+// hc_ps_select: idx = #{i : C_i <= tau} (-1: W = 0) with W and tau written; hc_ps_draw: one whole backward draw run
+// serially over the particles x [n][S] (xt = NULL: the terminal rule), the weights into q [n], the maximum into *m.
+float hc_ps_pair_logw(int model, const float* x, const float* xt, const float* th, float dt, float* dropped) {
+  using namespace vissm::ps;
+  switch (model) {
+    case VISSM_MODEL_AR: {
+      const Par p = prepare<VISSM_MODEL_AR>(th, dt);
+      *dropped = dropped_const<VISSM_MODEL_AR>(th, dt);
+      return pair_logw<VISSM_MODEL_AR>(particle<VISSM_MODEL_AR>(x, p), p, xt);
+    }
+    case VISSM_MODEL_LV: {
+      const Par p = prepare<VISSM_MODEL_LV>(th, dt);
+      *dropped = dropped_const<VISSM_MODEL_LV>(th, dt);
+      return pair_logw<VISSM_MODEL_LV>(particle<VISSM_MODEL_LV>(x, p), p, xt);
+    }
+    default: {
+      const Par p = prepare<VISSM_MODEL_FHN>(th, dt);
+      *dropped = dropped_const<VISSM_MODEL_FHN>(th, dt);
+      return pair_logw<VISSM_MODEL_FHN>(particle<VISSM_MODEL_FHN>(x, p), p, xt);
+    }
+  }
+}
+uint64_t hc_ps_threshold(uint32_t U, uint64_t W) { return vissm::ps::threshold(U, W); }
+uint32_t hc_ps_select_u(uint64_t seed, uint32_t t, uint64_t r) { return vissm::ps::select_u(seed, t, r); }
+int hc_ps_select(const uint64_t* q, int n, uint32_t U, uint64_t* W, uint64_t* tau) {
+  return vissm::ps::select(q, n, U, W, tau);
+}
+int hc_ps_draw(int model, const float* x, int n, const float* th, float dt, const float* xt, uint32_t U, uint64_t* q,
+               float* m) {
+  using namespace vissm::ps;
+  switch (model) {
+    case VISSM_MODEL_AR: return draw<VISSM_MODEL_AR>(x, n, th, dt, xt, U, q, m);
+    case VISSM_MODEL_LV: return draw<VISSM_MODEL_LV>(x, n, th, dt, xt, U, q, m);
+    default: return draw<VISSM_MODEL_FHN>(x, n, th, dt, xt, U, q, m);
+  }
+}
+int hc_ps_valid_m(int m, int n) { return vissm::ps::valid_m(m, n) ? 1 : 0; }
+
 // the C ABI's struct layouts as the C compiler sees them (the ctypes mirrors in viforssms_amd/_lib.py are
-// checked against these): which = 0 VissmFlowDesc, 1 VissmFlowParams, 2 VissmFlowGrads, 3 VissmElboData, 4 VissmColStatDesc, 5 VissmSimDesc, 6 VissmPfDesc; out = {size,
+// checked against these): which = 0 VissmFlowDesc, 1 VissmFlowParams, 2 VissmFlowGrads, 3 VissmElboData, 4 VissmColStatDesc, 5 VissmSimDesc, 6 VissmPfDesc, 7 VissmPsDesc; out = {size,
 // offset of the last field}
 void vissm_host_abi_layout(int which, size_t* out) {
   switch (which) {
@@ -92,6 +134,7 @@ void vissm_host_abi_layout(int which, size_t* out) {
     case 5: out[0] = sizeof(VissmSimDesc); out[1] = offsetof(VissmSimDesc, with_obs); break;
     case 4: out[0] = sizeof(VissmColStatDesc); out[1] = offsetof(VissmColStatDesc, n_ranks); break;
     case 6: out[0] = sizeof(VissmPfDesc); out[1] = offsetof(VissmPfDesc, obs_std); break;
+    case 7: out[0] = sizeof(VissmPsDesc); out[1] = offsetof(VissmPsDesc, dt); break;
     default: out[0] = sizeof(VissmElboData); out[1] = offsetof(VissmElboData, obs_stride); break;
   }
 }

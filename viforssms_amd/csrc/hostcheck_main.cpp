@@ -11,6 +11,7 @@
 // restatement with separate high and low multiplies, on a few thousand counters; u01 on the ends of its range;
 // the particle filter's quantised weights, thresholds and serial systematic resampling (pf_math.hpp) on their edge
 // cases against a 128-bit restatement;
+// the particle smoother's backward weights, integer selection and whole draws (ps_math.hpp) on theirs;
 // any sanitizer report aborts the run (-fno-sanitize-recover=all).
 // Exit 0 = all checks passed.  Not part of the product path.
 #include <cmath>
@@ -40,6 +41,12 @@ uint64_t hc_pf_threshold(uint32_t j, uint32_t U, uint64_t W, int log2n);
 uint32_t hc_pf_resample_u(uint64_t seed, uint32_t t, uint64_t r);
 uint64_t hc_pf_resample(const uint64_t* q, int n, uint32_t U, int32_t* anc, uint64_t* C);
 double hc_pf_ll_increment(float m, uint64_t W, int n);
+float hc_ps_pair_logw(int model, const float* x, const float* xt, const float* th, float dt, float* dropped);
+uint64_t hc_ps_threshold(uint32_t U, uint64_t W);
+uint32_t hc_ps_select_u(uint64_t seed, uint32_t t, uint64_t r);
+int hc_ps_select(const uint64_t* q, int n, uint32_t U, uint64_t* W, uint64_t* tau);
+int hc_ps_draw(int model, const float* x, int n, const float* th, float dt, const float* xt, uint32_t U, uint64_t* q,
+               float* m);
 }
 
 namespace {
@@ -422,6 +429,110 @@ int check_pf() {
   return bad;
 }
 
+// The particle smoother's shared math (ps_math.hpp).  The selection against a 128-bit restatement over U = 0 and
+// 2^32 - 1, N = 64 and 1024, all-equal weights (W = N 2^40: 2^50 at N = 1024), one live particle, runs of zeros and
+// W = 0; pair_logw plus the dropped constant against *_trans' lp; a whole draw with dead particles, with the terminal
+// rule, with a NaN target and with no live particle.
+int check_ps() {
+  int bad = 0;
+  const uint32_t Umax = 0xFFFFFFFFu;
+  for (int n : {64, 1024}) {
+    std::vector<std::vector<uint64_t>> cases;
+    std::vector<uint64_t> q(n, 1ull << 40);  // all equal
+    cases.push_back(q);
+    q[n - 1] -= 1;
+    cases.push_back(q);
+    std::fill(q.begin(), q.end(), 0ull);
+    q[n / 3] = 1ull << 40;  // one live particle
+    cases.push_back(q);
+    for (int i = 0; i < n; ++i) q[i] = (i / 5) % 2 ? 0ull : static_cast<uint64_t>(uniform(0.0, 1099511627776.0));
+    q[7] = 1ull << 40;  // runs of zeros
+    cases.push_back(q);
+    for (int i = 0; i < n; ++i) q[i] = i < n - 3 ? 0ull : 1ull;  // W = 3, zeros first
+    cases.push_back(q);
+    for (const auto& qc : cases)
+      for (uint32_t U : {0u, 1u, 0x7FFFFFFFu, 0x80000000u, Umax}) {
+        uint64_t W = 0, tau = 0, sum = 0;
+        const int idx = hc_ps_select(qc.data(), n, U, &W, &tau);
+        for (int i = 0; i < n; ++i) sum += qc[i];
+        const uint64_t want_tau = static_cast<uint64_t>((static_cast<unsigned __int128>(U) * sum) >> 32);
+        int want = 0;
+        uint64_t C = 0;
+        for (int i = 0; i < n; ++i) {
+          C += qc[i];
+          want += C <= want_tau;
+        }
+        if (W != sum || tau != want_tau || tau >= W || hc_ps_threshold(U, sum) != want_tau || idx != want ||
+            idx >= n || qc[idx] == 0) {
+          std::printf("ps: n %d U %u: idx %d want %d\n", n, U, idx, want);
+          ++bad;
+        }
+      }
+    std::vector<uint64_t> zero(n, 0);
+    uint64_t W = 1, tau = 1;
+    if (hc_ps_select(zero.data(), n, 5u, &W, &tau) != -1 || W != 0) { std::printf("ps: W = 0\n"); ++bad; }
+  }
+  if (hc_ps_threshold(Umax, 1ull << 50) != (1ull << 50) - (1ull << 18)) { std::printf("ps: threshold at 2^50\n"); ++bad; }
+  // pair_logw + the dropped constant = *_trans' lp
+  const float ths[4][5] = {{5.f, 0.5f, 1.0986123f, 0.f, 0.f}, {-0.6931472f, -5.9914646f, -1.2039728f, 0.f, 0.f},
+                           {0.f, 0.f, 0.f, 0.f, 0.f}, {0.6931472f, 1.f, 1.5f, -0.6931472f, -1.2039728f}};
+  const float dts[4] = {1.f, 0.1f, 0.1f, 0.1f};
+  for (int model : {0, 1, 3})
+    for (int rep = 0; rep < 200; ++rep) {
+      float x[2], xt[2];
+      for (int d = 0; d < 2; ++d) {
+        const double c = model == 0 ? 10.0 : model == 1 ? 100.0 : 1.0;
+        x[d] = static_cast<float>(c * uniform(0.5, 1.5));
+        xt[d] = static_cast<float>(x[d] + (model == 1 ? 5.0 : model == 0 ? 6.0 : 0.3) * uniform(-1.0, 1.0));
+      }
+      float dropped = 0.f;
+      const float lw = hc_ps_pair_logw(model, x, xt, ths[model], dts[model], &dropped);
+      const float lp = lp_of(model, x, xt, ths[model], dts[model]);
+      if (!std::isfinite(lw) || std::fabs((lw + dropped) - lp) > 2e-5f * std::fmax(1.f, std::fabs(lp))) {
+        std::printf("ps: model %d pair_logw %.9g + %.9g vs lp %.9g\n", model, lw, dropped, lp);
+        ++bad;
+      }
+    }
+  // a whole draw: LV, 64 particles, every fourth dead (NaN or outside the orthant)
+  {
+    const int n = 64;
+    std::vector<float> x(2 * n);
+    for (int i = 0; i < n; ++i) {
+      x[2 * i] = static_cast<float>(100.0 * uniform(0.9, 1.1));
+      x[2 * i + 1] = static_cast<float>(100.0 * uniform(0.9, 1.1));
+      if (i % 4 == 1) x[2 * i] = i % 8 == 1 ? NAN : -1.f;
+    }
+    const float xt[2] = {101.f, 99.f}, nan_t[2] = {NAN, 99.f};
+    std::vector<uint64_t> q(n, 7);
+    float m = 0.f;
+    for (uint32_t U : {0u, 0x12345678u, Umax}) {
+      int idx = hc_ps_draw(1, x.data(), n, ths[1], 0.1f, xt, U, q.data(), &m);
+      uint64_t top = 0;
+      for (int i = 0; i < n; ++i) {
+        if (i % 4 == 1 && q[i] != 0) { std::printf("ps: a dead particle has weight\n"); ++bad; }
+        top = std::max(top, q[i]);
+      }
+      if (idx < 0 || idx >= n || idx % 4 == 1 || q[idx] == 0 || top != (1ull << 40) || !std::isfinite(m)) {
+        std::printf("ps: draw U %u idx %d\n", U, idx);
+        ++bad;
+      }
+      idx = hc_ps_draw(1, x.data(), n, ths[1], 0.1f, nullptr, U, q.data(), &m);  // terminal: uniform over the live
+      for (int i = 0; i < n; ++i)
+        if (q[i] != (i % 4 == 1 ? 0ull : 1ull << 40)) { std::printf("ps: terminal weight %d\n", i); ++bad; }
+      if (idx < 0 || idx % 4 == 1 || m != 0.f) { std::printf("ps: terminal draw idx %d\n", idx); ++bad; }
+      if (hc_ps_draw(1, x.data(), n, ths[1], 0.1f, nan_t, U, q.data(), &m) != -1) { std::printf("ps: NaN target\n"); ++bad; }
+    }
+    for (int i = 0; i < n; ++i) x[2 * i + 1] = -2.f;  // no live particle
+    if (hc_ps_draw(1, x.data(), n, ths[1], 0.1f, xt, 9u, q.data(), &m) != -1 ||
+        hc_ps_draw(1, x.data(), n, ths[1], 0.1f, nullptr, 9u, q.data(), &m) != -1) {
+      std::printf("ps: no live particle\n");
+      ++bad;
+    }
+  }
+  if (hc_ps_select_u(1u, 2u, 3u) == hc_ps_select_u(1u, 3u, 3u)) { std::printf("ps: select_u\n"); ++bad; }
+  return bad;
+}
+
 }  // namespace
 
 int main() {
@@ -445,9 +556,10 @@ int main() {
   bad += check_sim_dead();
   bad += check_philox();
   bad += check_pf();
+  bad += check_ps();
   bad += check_colkey();
   bad += check_select();
-  for (int which = 0; which < 7; ++which) {
+  for (int which = 0; which < 8; ++which) {
     size_t out[2] = {0, 0};
     vissm_host_abi_layout(which, out);
     if (out[0] == 0 || out[1] >= out[0]) { std::printf("abi layout %d: %zu %zu\n", which, out[0], out[1]); ++bad; }

@@ -1045,3 +1045,71 @@ def particle_filter(model_id: int, theta: torch.Tensor, x_start: torch.Tensor, o
                                             ptr(state_end), ptr(cl), ptr(qt), ptr(at), _lib.stream_handle(dev)),
           "vissm_particle_filter")
     return ParticleFilterResult(loglik, ll_inc, ess, state_end, cl, qt, at)
+
+
+# ---------------------------------------------------------------------------------------
+# particle smoother (backward simulation over the filter's cloud: smoothing bands)
+# ---------------------------------------------------------------------------------------
+@dataclass
+class ParticleSmoothResult:
+    paths: torch.Tensor                  # [K M, S, H] backward trajectories (NaN where no particle could be drawn)
+    x_first: torch.Tensor                # [K M, S] = paths[:, :, 0]: the x_next of the call over the steps before
+    idx: Optional[torch.Tensor]          # [K M, H] int32 the chosen particle of each step (-1 where NaN), or None
+    q_trace: Optional[torch.Tensor]      # [K, H, M, N] int64 (the kernel's uint64 weights, at most 2^40), or None
+
+
+def particle_smooth(model_id: int, theta: torch.Tensor, cloud: torch.Tensor, dt: float, M: int, seed: int, row0: int,
+                    t0: int = 0, x_next: Optional[torch.Tensor] = None, idx: bool = False,
+                    trace: bool = False) -> ParticleSmoothResult:
+    """M backward-simulation trajectories per filter over cloud [K N, S, H], the equally weighted post-resampling
+    particles particle_filter wrote for theta [K, P] (raw); vissm_particle_smooth: one wave per block, one trajectory
+    per lane, the selection in integers.  Trajectory (k, j) draws its selection words from Philox row
+    row0 + k N + j under `seed` at counter (t0 + t, 2, row).  x_next [K M, S] is the target of the last step (None:
+    a uniform draw over the live particles there); a call over the steps before with x_next = this call's x_first
+    and its own t0 continues bitwise.  AR, LV and FHN; SV has no filter and is refused."""
+    if model_id not in _lib.MODEL_S:
+        raise _lib.VissmError(f"particle_smooth: unknown model {model_id}")
+    if model_id == _lib.MODEL_SV:
+        raise _lib.VissmError("particle_smooth: no particle filter for SV (its first coordinate is the observed "
+                              "series)")
+    S, P = _lib.MODEL_S[model_id], _lib.MODEL_P[model_id]
+    _require_gpu(theta, cloud)
+    for name, t in (("theta", theta), ("cloud", cloud)):
+        if t.dtype != torch.float32:
+            raise _lib.VissmError(f"particle_smooth: fp32 {name} expected, got {t.dtype}")
+    if theta.dim() != 2 or theta.shape[1] != P or theta.shape[0] < 1:
+        raise _lib.VissmError(f"particle_smooth: theta [K >= 1, {P}] expected, got {tuple(theta.shape)}")
+    K, M = theta.shape[0], int(M)
+    if cloud.dim() != 3 or cloud.shape[1] != S or cloud.shape[0] % K or not cloud.is_contiguous():
+        raise _lib.VissmError(f"particle_smooth: a contiguous cloud [{K} N, {S}, H] expected, got "
+                              f"{tuple(cloud.shape)}")
+    N, H, t0 = cloud.shape[0] // K, cloud.shape[2], int(t0)
+    if N not in _lib.PF_PARTICLES:
+        raise _lib.VissmError(f"particle_smooth: N={N} particles, one of {_lib.PF_PARTICLES} expected")
+    if not (_lib.PS_MIN_PATHS <= M <= N and M & (M - 1) == 0):
+        raise _lib.VissmError(f"particle_smooth: M={M} trajectories, a power of two in {_lib.PS_MIN_PATHS} .. N = {N} "
+                              "expected")
+    if K > 65535:
+        raise _lib.VissmError(f"particle_smooth: K={K} filters, at most 65535 per call")
+    if H < 1 or t0 < 0 or t0 + H >= 2 ** 31:
+        raise _lib.VissmError(f"particle_smooth: bad horizon H={H} t0={t0} (H >= 1 and t0 + H below 2^31)")
+    if not 0 <= int(row0) < 2 ** 64:
+        raise _lib.VissmError(f"particle_smooth: row0={row0} outside [0, 2^64)")
+    dev = theta.device
+    if cloud.device != dev:
+        raise _lib.VissmError("particle_smooth: all tensors on one device expected")
+    theta = theta.contiguous()
+    if x_next is not None:
+        if not x_next.is_cuda or x_next.device != dev or x_next.dtype != torch.float32 or \
+                tuple(x_next.shape) != (K * M, S) or not x_next.is_contiguous():
+            raise _lib.VissmError(f"particle_smooth: x_next: a contiguous fp32 GPU tensor [{K * M}, {S}] expected")
+    paths = torch.empty(K * M, S, H, dtype=torch.float32, device=dev)
+    x_first = torch.empty(K * M, S, dtype=torch.float32, device=dev)
+    ix = torch.empty(K * M, H, dtype=torch.int32, device=dev) if idx else None
+    qt = torch.empty(K, H, M, N, dtype=torch.int64, device=dev) if trace else None
+    d = _lib.PsDesc(model_id, K, N, M, H, t0, float(dt))
+    check(_lib.load().vissm_particle_smooth(ctypes.byref(d), ctypes.c_uint64(seed & (2 ** 64 - 1)),
+                                            ctypes.c_uint64(int(row0)), ptr(theta), ptr(cloud), ptr(x_next),
+                                            ptr(paths), ptr(x_first), ptr(ix), ptr(qt), _lib.stream_handle(dev)),
+          "vissm_particle_smooth")
+    return ParticleSmoothResult(paths, x_first, ix, qt)

@@ -25,6 +25,10 @@ from .summary import DEFAULT_PROBS, _check_probs, column_summary
 FORECAST_SEED_XOR = 0xF02ECA57
 # Philox key of the particle filter's normals and resampling integers: a fourth key next to the forecast's
 FILTER_SEED_XOR = 0xF117E2ED
+# Philox key of the particle smoother's selection words: a fifth key
+SMOOTH_SEED_XOR = 0x5300714E
+# device bytes of the filter's cloud [K N, S, T] fp32 that particle_smoother() may keep for its backward pass
+SMOOTH_CLOUD_BYTES = 8 << 30
 # device bytes one forecast launch may write per output ([B, S, chunk] fp32): the default chunk is the largest
 # multiple of the kernel's tile under it
 FORECAST_CHUNK_BYTES = 256 << 20
@@ -713,10 +717,16 @@ class VISSMBase:
         observations' length).  Philox key seed ^ FILTER_SEED_XOR, rows global_step K N + k N + i; `chunk` steps per
         launch (default filter_chunk()), chained through the end state and the running log-likelihood, change
         nothing.  SV has no observation model: ValueError."""
+        return self._filter_pass(n_theta, n_particles, probs, chunk, None)[0]
+
+    def _filter_pass(self, n_theta, n_particles, probs, chunk, keep):
+        """particle_filter()'s launches and result; with keep = (M, cap) the arguments of particle_smoother() are
+        checked before the first launch and every chunk's cloud stays on the device: (res, theta, [(t0, cloud)])."""
         from . import ops
         md = self.mdef
+        what = "particle_filter" if keep is None else "particle_smoother"
         if md.model_id == _lib.MODEL_SV or getattr(self, "filter_data", None) is None:
-            raise ValueError("particle_filter: SV has no observation model (its first coordinate is the observed "
+            raise ValueError(f"{what}: SV has no observation model (its first coordinate is the observed "
                              "series)")
         K, N = int(n_theta), int(n_particles)
         if N not in _lib.PF_PARTICLES:
@@ -731,6 +741,17 @@ class VISSMBase:
         S, Q = _lib.MODEL_S[md.model_id], p.size
         obs_h, bin_h, x0_h = self.filter_data
         T = min(int(self.target_len()), obs_h.shape[1])
+        if keep is not None:
+            M, cap = keep
+            if not (_lib.PS_MIN_PATHS <= M <= N and M & (M - 1) == 0):
+                raise ValueError(f"particle_smoother: n_paths={M}, a power of two in {_lib.PS_MIN_PATHS} .. "
+                                 f"n_particles = {N} expected")
+            if T < 1:
+                raise ValueError("particle_smoother: no step to smooth")
+            if 4 * K * N * S * T > cap:
+                raise ValueError(f"particle_smoother: the filter's cloud [{K} * {N}, {S}, {T}] fp32 takes "
+                                 f"{4 * K * N * S * T} bytes, more than SMOOTH_CLOUD_BYTES = {cap}: lower n_theta or "
+                                 "n_particles")
         obs = torch.as_tensor(np.ascontiguousarray(obs_h[:, :T]), device=dev)
         obs_bin = torch.as_tensor(np.ascontiguousarray(bin_h[:, :T]), device=dev)
         x0 = torch.as_tensor(x0_h, device=dev)
@@ -743,7 +764,7 @@ class VISSMBase:
         seed = self.engine.seed ^ FILTER_SEED_XOR
         row0 = self.global_step * K * N
         state, ll = x0, None
-        incs, esss, parts = [], [], []
+        incs, esss, parts, clouds = [], [], [], []
         for t0 in range(0, T, chunk):
             m = min(chunk, T - t0)
             r = ops.particle_filter(md.model_id, th, state, obs, obs_bin, md.dt, md.obs_std, N, seed, row0, t0=t0,
@@ -752,6 +773,8 @@ class VISSMBase:
             incs.append(r.ll_inc)
             esss.append(r.ess)
             parts.append((m, column_summary(r.cloud.view(K * N, S * m), probs, None)))
+            if keep is not None:
+                clouds.append((t0, r.cloud))
         res: Dict[str, np.ndarray] = {"probs": p, "filter/theta": th.cpu().numpy()}
         res["filter/loglik"] = ll.cpu().numpy() if ll is not None else np.zeros(K)
         res["filter/ll_inc"] = torch.cat(incs + [torch.zeros(K, 0, device=dev)], 1).cpu().numpy()
@@ -761,12 +784,63 @@ class VISSMBase:
                                                 [np.zeros((S, 0), dtype=dt_)], axis=1)
         res["filter/quantiles"] = np.concatenate([s["quantiles"].reshape(Q, S, m) for m, s in parts] +
                                                  [np.zeros((Q, S, 0))], axis=2)
-        return res
+        return res, th, clouds
 
     def save_filter(self, PATH: str, n_theta: int = 64, n_particles: int = 1024, probs=DEFAULT_PROBS,
                     chunk: Optional[int] = None) -> Dict[str, np.ndarray]:
         """particle_filter written as one .npz by rank 0 (every rank computes the same result)."""
         res = self.particle_filter(n_theta, n_particles, probs, chunk)
+        if self.dist.rank == 0:
+            d = os.path.dirname(PATH)
+            if d:
+                os.makedirs(d, exist_ok=True)
+            with open(PATH, "wb") as f:
+                np.savez(f, **res)
+        return res
+
+    # ------------------------------------------------------------------ particle smoother
+    @torch.no_grad()
+    def particle_smoother(self, n_theta: int = 64, n_particles: int = 1024, n_paths: int = 64, probs=DEFAULT_PROBS,
+                          chunk: Optional[int] = None) -> Dict[str, np.ndarray]:
+        """The check that is comparable with what the engine fits: the variational posterior over the latent path is
+        a smoothing distribution p(x_t | y_1:T), the filter's bands are filtering distributions p(x_t | y_1:t).
+        Forward filtering, then backward simulation (ops.particle_smooth): the forward pass is particle_filter()'s,
+        launch for launch (same theta rows, key, rows and chunks), with every chunk's cloud kept on the device --
+        4 K N S T bytes, refused with ValueError before any launch above SMOOTH_CLOUD_BYTES; then M = n_paths
+        trajectories per filter (a power of two, 64 <= M <= N) are drawn backward through the chunks, last to first,
+        each chunk's first state the target of the one before, under the key seed ^ SMOOTH_SEED_XOR and rows
+        global_step K N + k N + j.
+
+        Returns every filter/* entry of particle_filter() plus smooth/{mean, sd, n_valid} [S, T] and
+        smooth/quantiles [Q, S, T], the column summary of the K M trajectories of each step: the smoothing
+        distribution averaged over q(theta), to lay over paths/quantiles of posterior_summary().  A filter that died
+        contributes NaN trajectories, which n_valid leaves out.  `chunk` changes nothing; every rank runs the same
+        launches and holds the same result.  SV has no observation model: ValueError."""
+        from . import ops
+        md = self.mdef
+        K, N, M = int(n_theta), int(n_particles), int(n_paths)
+        res, th, clouds = self._filter_pass(K, N, probs, chunk, (M, SMOOTH_CLOUD_BYTES))
+        S, Q = _lib.MODEL_S[md.model_id], res["probs"].size
+        seed = self.engine.seed ^ SMOOTH_SEED_XOR
+        row0 = self.global_step * K * N
+        parts, x_next = [], None
+        while clouds:
+            t0, cloud = clouds.pop()          # last chunk first; the cloud is freed once it is smoothed
+            r = ops.particle_smooth(md.model_id, th, cloud, md.dt, M, seed, row0, t0=t0, x_next=x_next)
+            x_next = r.x_first
+            m = cloud.shape[2]
+            parts.append((m, column_summary(r.paths.view(K * M, S * m), probs, None)))
+            del cloud, r
+        parts.reverse()
+        for k in ("mean", "sd", "n_valid"):
+            res[f"smooth/{k}"] = np.concatenate([s[k].reshape(S, m) for m, s in parts], axis=1)
+        res["smooth/quantiles"] = np.concatenate([s["quantiles"].reshape(Q, S, m) for m, s in parts], axis=2)
+        return res
+
+    def save_smoother(self, PATH: str, n_theta: int = 64, n_particles: int = 1024, n_paths: int = 64,
+                      probs=DEFAULT_PROBS, chunk: Optional[int] = None) -> Dict[str, np.ndarray]:
+        """particle_smoother written as one .npz by rank 0 (every rank computes the same result)."""
+        res = self.particle_smoother(n_theta, n_particles, n_paths, probs, chunk)
         if self.dist.rank == 0:
             d = os.path.dirname(PATH)
             if d:
