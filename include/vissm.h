@@ -641,6 +641,8 @@ int vissm_sde_simulate(const VissmSimDesc* d, uint64_t seed, uint64_t row0,
  * its loglik continues bitwise.  No workspace, no float atomics, fixed-order double sums: two launches are bitwise
  * equal, and filter k's bits depend on (seed, row0 + k N, theta_k, N, data) only, not on K or the block index.
  * vissm_particle_filter_lds_bytes: the LDS one block declares (host arithmetic; 0 = bad model or N).
+ * vissm_particle_filter_adapted, below, takes the same arguments and gives an estimate of far smaller variance where
+ * obs_std is small against the process noise.
  * ------------------------------------------------------------------------- */
 typedef struct {
   int32_t model, K, N, H, t0, T_total;
@@ -655,6 +657,37 @@ int vissm_particle_filter(const VissmPfDesc* d, uint64_t seed, uint64_t row0,
                           float* ll_inc /* [K][H] */, float* ess /* [K][H] */, float* state_end /* [K N][S] */,
                           float* cloud /* [K N][S][H] or NULL */, uint64_t* q_trace /* [K][H][N] or NULL */,
                           int32_t* anc_trace /* [K][H][N] or NULL */, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Fully adapted auxiliary particle filter of the same three models: the descriptor, arguments, geometry, Philox
+ * streams, integer pipeline, outputs, chaining and refusals of vissm_particle_filter, with a lower-variance estimate
+ * of log p(y | theta).  The Euler-Maruyama transition is Gaussian given the previous state, x' | x ~ N(mu(x),
+ * Sigma(x)), and the observation reads the coordinates O = {d : bin_d != 0} with N(0, R) noise, R = obs_std^2, so
+ * both the predictive p(y_t | x_t-1) and the conditional p(x_t | x_t-1, y_t) are Gaussian (csrc/gp_math.hpp).
+ *
+ * An unobserved step is vissm_particle_filter's, bitwise.  At an observed step
+ *   logw_i = log N(y_O; mu_O(x_i), Sigma_OO(x_i) + R I) of the particle's *pre-step* state x_i (fp32);
+ *   m, q_i, W, ll_inc, ess, U, tau_j and anc[j] from these logw_i exactly as above;
+ *   slot j takes the pre-step state of particle anc[j] and draws x'_j = m + L n from its conditional,
+ *   m = mu + K (y_O - mu_O), K = Sigma_.O (Sigma_OO + R I)^-1, L L^T = Sigma - K Sigma_O. (lower, coordinate order),
+ *   with n the S normals of its own Philox row at this step; then the death rule.
+ * A coordinate is observed iff bin_d != 0 (the value is otherwise unused; the bootstrap filter multiplies by it, and
+ * the two agree for 0 / 1).  The cloud holds the post-propagation particles, an equally weighted sample of
+ * p(x_t | y_1:t, theta), so vissm_particle_smooth runs on it unchanged.  Unlike the bootstrap's it may hold dead (NaN)
+ * particles at observed steps of LV, where a draw can leave the orthant after the resampling; they get q = 0 at the
+ * next observed step, the second-stage weight of the killed model, so the estimate stays that of the model
+ * vissm_particle_filter estimates.  Also refused: obs_std <= 0 or not finite (the conditional degenerates).
+ * vissm_particle_filter_adapted_lds_bytes = vissm_particle_filter_lds_bytes (the same arrays).
+ * ------------------------------------------------------------------------- */
+int32_t vissm_particle_filter_adapted_lds_bytes(int32_t model, int32_t N);
+int vissm_particle_filter_adapted(const VissmPfDesc* d, uint64_t seed, uint64_t row0,
+                                  const float* theta /* [K][P] */, const float* x_start /* [K N][S] */,
+                                  const float* obs /* [S][T_total] */, const float* obs_bin /* [S][T_total] */,
+                                  const double* loglik_in /* [K] or NULL */, double* loglik /* [K] */,
+                                  float* ll_inc /* [K][H] */, float* ess /* [K][H] */,
+                                  float* state_end /* [K N][S] */, float* cloud /* [K N][S][H] or NULL */,
+                                  uint64_t* q_trace /* [K][H][N] or NULL */,
+                                  int32_t* anc_trace /* [K][H][N] or NULL */, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Particle smoother: forward filtering, backward simulation (FFBSi) over the cloud vissm_particle_filter wrote.  The

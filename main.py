@@ -54,9 +54,11 @@ def run(argv=None):
     if args.forecast:
         model.save_forecast(args.forecast[1], args.forecast[0])   # every rank, as the summary
     if args.filter:
-        model.save_filter(args.filter[2], args.filter[0], args.filter[1])   # every rank the same launches; rank 0 writes
+        # every rank the same launches; rank 0 writes
+        model.save_filter(args.filter[2], args.filter[0], args.filter[1], proposal=args.filter_proposal)
     if args.smooth:
-        model.save_smoother(args.smooth[3], args.smooth[0], args.smooth[1], args.smooth[2])   # as the filter
+        model.save_smoother(args.smooth[3], args.smooth[0], args.smooth[1], args.smooth[2],
+                            proposal=args.filter_proposal)   # as the filter
     return model
 
 

@@ -211,6 +211,8 @@ SIGNATURES = {
                                   _c_void_p, _c_void_p]),
     "vissm_particle_filter_lds_bytes": (_i32, [_i32, _i32]),
     "vissm_particle_filter": (_i32, [ctypes.POINTER(PfDesc), _u64, _u64] + [_c_void_p] * 12 + [_c_void_p]),
+    "vissm_particle_filter_adapted_lds_bytes": (_i32, [_i32, _i32]),
+    "vissm_particle_filter_adapted": (_i32, [ctypes.POINTER(PfDesc), _u64, _u64] + [_c_void_p] * 12 + [_c_void_p]),
     "vissm_particle_smooth_lds_bytes": (_i32, [_i32, _i32, _i32]),
     "vissm_particle_smooth": (_i32, [ctypes.POINTER(PsDesc), _u64, _u64] + [_c_void_p] * 7 + [_c_void_p]),
     "vissm_profile_enable": (None, [_i32]),

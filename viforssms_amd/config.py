@@ -143,7 +143,16 @@ def handle_opts(argv=None):
                         help="After training, run the K particle filters of N particles of --filter and then draw M "
                              "smoothing trajectories per filter by backward simulation on the GPU (M a power of two, "
                              "64 <= M <= N), and write the filter's entries and the smoothing bands to this .npz file")
+    parser.add_argument("--filter-proposal", choices=("bootstrap", "adapted"), default=None,
+                        help="The proposal of the particle filters of --filter and --smooth: bootstrap (the default) "
+                             "propagates blindly and weights on the observation; adapted weights on the predictive "
+                             "p(y_t | x_t-1) and propagates from p(x_t | x_t-1, y_t), a much lower variance of the "
+                             "log-evidence where obs_std is small against the process noise")
     args = parser.parse_args(argv)
+    if args.filter_proposal is not None and args.filter is None and args.smooth is None:
+        parser.error("--filter-proposal applies to --filter and --smooth: give one of them")
+    if args.filter_proposal is None:
+        args.filter_proposal = "bootstrap"
     if args.smooth is not None:
         try:
             args.smooth = (int(args.smooth[0]), int(args.smooth[1]), int(args.smooth[2]), args.smooth[3])

@@ -3,7 +3,8 @@
 // of sim_math.hpp (the forecast kernel's Euler-Maruyama steps) against a float64 restatement,
 // of rng_math.hpp (Philox4x32-10 and u01) against tests/philox_ref.py,
 // of pf_math.hpp (the particle filter's integer weights and resampling) against Python big-int arithmetic,
-// and of ps_math.hpp (the particle smoother's backward weights and integer selection) against float64 and big ints.
+// of ps_math.hpp (the particle smoother's backward weights and integer selection) against float64 and big ints,
+// and of gp_math.hpp (the adapted filter's predictive weight and conditional draw) against numpy.linalg in float64.
 // Not part of the product path: libvissm_hostcheck.so is loaded only by tests/.
 #include <cstddef>
 
@@ -14,6 +15,7 @@
 #include "rng_math.hpp"
 #include "pf_math.hpp"
 #include "ps_math.hpp"
+#include "gp_math.hpp"
 
 extern "C" {
 
@@ -122,6 +124,113 @@ int hc_ps_draw(int model, const float* x, int n, const float* th, float dt, cons
   }
 }
 int hc_ps_valid_m(int m, int n) { return vissm::ps::valid_m(m, n) ? 1 : 0; }
+
+// The adapted filter's shared math (gp_math.hpp: the code particle_filter_kernel<.., kAdapted> runs) for the pre-step
+// state x, raw theta and R = obs_std^2.  hc_gp_moments: out = [mu0, mu1, S00, S01, S11, det]; hc_gp_logw: the
+// predictive log-weight; hc_gp_cond: out = [m0, m1, l00, l10, l11]; hc_gp_step: the conditional draw from normals
+// n[0 .. S), without the death rule; hc_gp_l11: the clamped sqrt(P11 - l10^2).  hc_gp_filter_step: one adapted filter
+// step of n particles x [n][S] run serially -- unobserved (every bin 0): sim::advance; observed: weights q [n] of the
+// pre-step states, serial systematic resampling with U into anc [n] (C [n] scratch), then x_out[j] drawn from
+// ancestor anc[j]'s state with normals[j], death rule applied.  Returns W (0: the filter is dead, x_out all NaN; 1 at
+// an unobserved step); *m_out the maximum log-weight.
+extern "C++" {
+namespace {
+template <int MODEL>
+void gp_moments_t(const float* x, const float* th, float dt, float* out) {
+  const vissm::gp::Moments mo = vissm::gp::moments<MODEL>(x, vissm::sim::prepare<MODEL>(th, dt));
+  out[0] = mo.mu[0]; out[1] = mo.mu[1]; out[2] = mo.s00; out[3] = mo.s01; out[4] = mo.s11; out[5] = mo.det;
+}
+template <int MODEL>
+void gp_cond_t(const float* x, const float* th, float dt, const float* y, const float* bin, float R, float* out) {
+  using namespace vissm;
+  const gp::Cond c = gp::cond<VISSM_MODEL_S(MODEL)>(gp::moments<MODEL>(x, sim::prepare<MODEL>(th, dt)), y, bin, R);
+  out[0] = c.m[0]; out[1] = c.m[1]; out[2] = c.l00; out[3] = c.l10; out[4] = c.l11;
+}
+template <int MODEL>
+uint64_t gp_filter_step_t(const float* x, int n, const float* th, float dt, const float* y, const float* bin,
+                          float obs_std, const float* normals, uint32_t U, float* x_out, uint64_t* q, int32_t* anc,
+                          uint64_t* C, float* m_out) {
+  using namespace vissm;
+  constexpr int S = VISSM_MODEL_S(MODEL);
+  const sim::Par p = sim::prepare<MODEL>(th, dt);
+  const float R = obs_std * obs_std;
+  bool observed = false;
+  for (int d = 0; d < S; ++d) observed = observed || bin[d] != 0.f;
+  *m_out = 0.f;
+  if (!observed) {
+    for (int i = 0; i < n; ++i) {
+      for (int d = 0; d < S; ++d) x_out[i * S + d] = x[i * S + d];
+      sim::advance<MODEL>(x_out + i * S, p, normals + i * S, 0.f, nullptr);
+      q[i] = 0;
+      anc[i] = i;
+    }
+    return 1;
+  }
+  float m = -__builtin_inff();
+  for (int pass = 0; pass < 2; ++pass)
+    for (int i = 0; i < n; ++i) {
+      const bool ok = sim::alive(MODEL, x + i * S);
+      const float lw = ok ? gp::state_logw<MODEL>(x + i * S, p, y, bin, R) : -__builtin_inff();
+      if (pass == 0) m = lw > m ? lw : m;
+      else q[i] = pf::quantise(lw, m, ok);
+    }
+  *m_out = m;
+  const uint64_t W = pf::resample(q, n, U, anc, C);
+  for (int j = 0; j < n; ++j)
+    for (int d = 0; d < S; ++d) x_out[j * S + d] = W ? x[anc[j] * S + d] : sim::quiet_nan();
+  if (W)
+    for (int j = 0; j < n; ++j) gp::advance<MODEL>(x_out + j * S, p, y, bin, R, normals + j * S);
+  return W;
+}
+}  // namespace
+}  // extern "C++"
+
+void hc_gp_moments(int model, const float* x, const float* th, float dt, float* out) {
+  switch (model) {
+    case VISSM_MODEL_AR: gp_moments_t<VISSM_MODEL_AR>(x, th, dt, out); break;
+    case VISSM_MODEL_LV: gp_moments_t<VISSM_MODEL_LV>(x, th, dt, out); break;
+    default: gp_moments_t<VISSM_MODEL_FHN>(x, th, dt, out); break;
+  }
+}
+float hc_gp_logw(int model, const float* x, const float* th, float dt, const float* y, const float* bin, float R) {
+  using namespace vissm;
+  switch (model) {
+    case VISSM_MODEL_AR: return gp::state_logw<VISSM_MODEL_AR>(x, sim::prepare<VISSM_MODEL_AR>(th, dt), y, bin, R);
+    case VISSM_MODEL_LV: return gp::state_logw<VISSM_MODEL_LV>(x, sim::prepare<VISSM_MODEL_LV>(th, dt), y, bin, R);
+    default: return gp::state_logw<VISSM_MODEL_FHN>(x, sim::prepare<VISSM_MODEL_FHN>(th, dt), y, bin, R);
+  }
+}
+void hc_gp_cond(int model, const float* x, const float* th, float dt, const float* y, const float* bin, float R,
+                float* out) {
+  switch (model) {
+    case VISSM_MODEL_AR: gp_cond_t<VISSM_MODEL_AR>(x, th, dt, y, bin, R, out); break;
+    case VISSM_MODEL_LV: gp_cond_t<VISSM_MODEL_LV>(x, th, dt, y, bin, R, out); break;
+    default: gp_cond_t<VISSM_MODEL_FHN>(x, th, dt, y, bin, R, out); break;
+  }
+}
+void hc_gp_step(int model, const float* x, const float* th, float dt, const float* y, const float* bin, float R,
+                const float* n, float* out) {
+  using namespace vissm;
+  for (int d = 0; d < VISSM_MODEL_S(model); ++d) out[d] = x[d];
+  switch (model) {
+    case VISSM_MODEL_AR: gp::step<VISSM_MODEL_AR>(out, sim::prepare<VISSM_MODEL_AR>(th, dt), y, bin, R, n); break;
+    case VISSM_MODEL_LV: gp::step<VISSM_MODEL_LV>(out, sim::prepare<VISSM_MODEL_LV>(th, dt), y, bin, R, n); break;
+    default: gp::step<VISSM_MODEL_FHN>(out, sim::prepare<VISSM_MODEL_FHN>(th, dt), y, bin, R, n); break;
+  }
+}
+float hc_gp_l11(float p11, float l10) { return vissm::gp::chol_l11(p11, l10); }
+uint64_t hc_gp_filter_step(int model, const float* x, int n, const float* th, float dt, const float* y,
+                           const float* bin, float obs_std, const float* normals, uint32_t U, float* x_out,
+                           uint64_t* q, int32_t* anc, uint64_t* C, float* m_out) {
+  switch (model) {
+    case VISSM_MODEL_AR:
+      return gp_filter_step_t<VISSM_MODEL_AR>(x, n, th, dt, y, bin, obs_std, normals, U, x_out, q, anc, C, m_out);
+    case VISSM_MODEL_LV:
+      return gp_filter_step_t<VISSM_MODEL_LV>(x, n, th, dt, y, bin, obs_std, normals, U, x_out, q, anc, C, m_out);
+    default:
+      return gp_filter_step_t<VISSM_MODEL_FHN>(x, n, th, dt, y, bin, obs_std, normals, U, x_out, q, anc, C, m_out);
+  }
+}
 
 // the C ABI's struct layouts as the C compiler sees them (the ctypes mirrors in viforssms_amd/_lib.py are
 // checked against these): which = 0 VissmFlowDesc, 1 VissmFlowParams, 2 VissmFlowGrads, 3 VissmElboData, 4 VissmColStatDesc, 5 VissmSimDesc, 6 VissmPfDesc, 7 VissmPsDesc; out = {size,

@@ -12,6 +12,9 @@
 // the particle filter's quantised weights, thresholds and serial systematic resampling (pf_math.hpp) on their edge
 // cases against a 128-bit restatement;
 // the particle smoother's backward weights, integer selection and whole draws (ps_math.hpp) on theirs;
+// the adapted filter's predictive weight, conditional mean and Cholesky factor (gp_math.hpp) against a double
+// restatement of the general 2 x 2 formulas over every mask and obs_std from 0.05 to 1000 transition sd, the clamp,
+// and whole serial filter steps with dead particles;
 // any sanitizer report aborts the run (-fno-sanitize-recover=all).
 // Exit 0 = all checks passed.  Not part of the product path.
 #include <cmath>
@@ -47,6 +50,16 @@ uint32_t hc_ps_select_u(uint64_t seed, uint32_t t, uint64_t r);
 int hc_ps_select(const uint64_t* q, int n, uint32_t U, uint64_t* W, uint64_t* tau);
 int hc_ps_draw(int model, const float* x, int n, const float* th, float dt, const float* xt, uint32_t U, uint64_t* q,
                float* m);
+void hc_gp_moments(int model, const float* x, const float* th, float dt, float* out);
+float hc_gp_logw(int model, const float* x, const float* th, float dt, const float* y, const float* bin, float R);
+void hc_gp_cond(int model, const float* x, const float* th, float dt, const float* y, const float* bin, float R,
+                float* out);
+void hc_gp_step(int model, const float* x, const float* th, float dt, const float* y, const float* bin, float R,
+                const float* n, float* out);
+float hc_gp_l11(float p11, float l10);
+uint64_t hc_gp_filter_step(int model, const float* x, int n, const float* th, float dt, const float* y,
+                           const float* bin, float obs_std, const float* normals, uint32_t U, float* x_out,
+                           uint64_t* q, int32_t* anc, uint64_t* C, float* m_out);
 }
 
 namespace {
@@ -533,6 +546,135 @@ int check_ps() {
   return bad;
 }
 
+// gp_math.hpp against the general formulas in double: S = Sigma_OO + R I, logw = log N(y_O; mu_O, S),
+// K = Sigma_.O S^-1, m = mu + K (y_O - mu_O), P = Sigma - K Sigma_O. = L L^T
+int check_gp() {
+  int bad = 0;
+  const float ths[4][5] = {{5.f, 0.5f, 1.0986123f, 0.f, 0.f}, {-0.6931472f, -5.9914646f, -1.2039728f, 0.f, 0.f},
+                           {0.f, 0.f, 0.f, 0.f, 0.f}, {0.6931472f, 1.f, 1.5f, -0.6931472f, -1.2039728f}};
+  const float dts[4] = {1.f, 0.1f, 0.1f, 0.1f};
+  const float masks[3][2] = {{1.f, 1.f}, {1.f, 0.f}, {0.f, 1.f}};
+  for (int model : {0, 1, 3}) {
+    const int S = model == 0 ? 1 : 2;
+    for (int mk = 0; mk < (S == 1 ? 1 : 3); ++mk)
+      for (double rel : {0.05, 0.5, 1.0, 30.0, 1000.0})
+        for (int rep = 0; rep < 40; ++rep) {
+          float x[2], y[2], n[2], mo[6], co[5], out[2];
+          const double c = model == 0 ? 10.0 : model == 1 ? 100.0 : 1.0;
+          for (int d = 0; d < 2; ++d) {
+            x[d] = static_cast<float>(c * uniform(0.5, 1.5));
+            n[d] = static_cast<float>(uniform(-2.0, 2.0));
+          }
+          hc_gp_moments(model, x, ths[model], dts[model], mo);
+          const double mu[2] = {mo[0], mo[1]}, Sg[2][2] = {{mo[2], mo[3]}, {mo[3], mo[4]}};
+          const float* bin = S == 1 ? masks[1] : masks[mk];
+          const double sd0 = std::sqrt(bin[0] != 0.f ? Sg[0][0] : Sg[1][1]);
+          const float obs_std = static_cast<float>(rel * sd0);
+          const float Rf = obs_std * obs_std;
+          const double R = Rf;
+          for (int d = 0; d < 2; ++d)  // an unobserved coordinate's y is a filler that must not be read
+            y[d] = bin[d] != 0.f ? static_cast<float>(mu[d] + std::sqrt(Sg[d][d] + R) * uniform(-2.0, 2.0)) : NAN;
+          int O[2], no = 0;
+          for (int d = 0; d < S; ++d)
+            if (bin[d] != 0.f) O[no++] = d;
+          double Sm[2][2] = {{1.0, 0.0}, {0.0, 1.0}}, r[2] = {0.0, 0.0};
+          for (int a = 0; a < no; ++a) {
+            r[a] = y[O[a]] - mu[O[a]];
+            for (int b = 0; b < no; ++b) Sm[a][b] = Sg[O[a]][O[b]] + (a == b ? R : 0.0);
+          }
+          const double det = Sm[0][0] * Sm[1][1] - Sm[0][1] * Sm[1][0];
+          const double Si[2][2] = {{Sm[1][1] / det, -Sm[0][1] / det}, {-Sm[1][0] / det, Sm[0][0] / det}};
+          double quad = 0.0;
+          for (int a = 0; a < no; ++a)
+            for (int b = 0; b < no; ++b) quad += r[a] * Si[a][b] * r[b];
+          const double lw = -0.5 * quad - 0.5 * std::log(det) - 0.5 * no * std::log(2.0 * M_PI);
+          double K[2][2] = {{0.0, 0.0}, {0.0, 0.0}}, m[2], P[2][2];
+          for (int d = 0; d < S; ++d)
+            for (int a = 0; a < no; ++a)
+              for (int b = 0; b < no; ++b) K[d][a] += Sg[d][O[b]] * Si[b][a];
+          for (int d = 0; d < S; ++d) {
+            m[d] = mu[d];
+            for (int a = 0; a < no; ++a) m[d] += K[d][a] * r[a];
+            for (int e = 0; e < S; ++e) {
+              P[d][e] = Sg[d][e];
+              for (int a = 0; a < no; ++a) P[d][e] -= K[d][a] * Sg[O[a]][e];
+            }
+          }
+          const float got = hc_gp_logw(model, x, ths[model], dts[model], y, bin, Rf);
+          hc_gp_cond(model, x, ths[model], dts[model], y, bin, Rf, co);
+          hc_gp_step(model, x, ths[model], dts[model], y, bin, Rf, n, out);
+          bool ok = std::isfinite(got) && std::fabs(got - lw) <= 2e-5 * std::fmax(1.0, std::fabs(lw));
+          for (int d = 0; d < S; ++d) ok = ok && std::fabs(co[d] - m[d]) <= 2e-5 * std::fmax(1.0, std::fabs(m[d]));
+          // L L^T = P to fp32 rounding of Sigma's entries (P itself cancels at small R)
+          const double ll[2][2] = {{double(co[2]) * co[2], double(co[2]) * co[3]},
+                                   {double(co[2]) * co[3], double(co[3]) * co[3] + double(co[4]) * co[4]}};
+          for (int d = 0; d < S; ++d)
+            for (int e = 0; e < S; ++e)
+              ok = ok && std::fabs(ll[d][e] - P[d][e]) <= 2e-5 * std::sqrt(Sg[d][d] * Sg[e][e]);
+          ok = ok && out[0] == co[0] + co[2] * n[0];
+          if (S == 2) ok = ok && std::fabs(out[1] - (co[1] + (co[3] * n[0] + co[4] * n[1]))) <= 1e-5 * std::fabs(co[1]);
+          if (!ok) {
+            std::printf("gp: model %d mask %d rel %g: logw %.9g vs %.9g, m %.9g %.9g vs %.9g %.9g\n", model, mk, rel, got,
+                        lw, co[0], co[1], m[0], S == 2 ? m[1] : 0.0);
+            ++bad;
+          }
+        }
+  }
+  // the clamp: a radicand that rounds negative gives 0, a NaN one stays NaN
+  if (hc_gp_l11(1.f, 1.0000001f) != 0.f || hc_gp_l11(4.f, 0.f) != 2.f || !std::isnan(hc_gp_l11(NAN, 1.f))) {
+    std::printf("gp: clamp\n");
+    ++bad;
+  }
+  // whole steps: LV, 64 particles, every fourth dead
+  {
+    const int n = 64;
+    std::vector<float> x(2 * n), nn(2 * n), xo(2 * n);
+    for (int i = 0; i < n; ++i) {
+      x[2 * i] = static_cast<float>(100.0 * uniform(0.9, 1.1));
+      x[2 * i + 1] = static_cast<float>(100.0 * uniform(0.9, 1.1));
+      if (i % 4 == 1) x[2 * i] = i % 8 == 1 ? NAN : -1.f;
+      nn[2 * i] = static_cast<float>(uniform(-2.0, 2.0));
+      nn[2 * i + 1] = static_cast<float>(uniform(-2.0, 2.0));
+    }
+    std::vector<uint64_t> q(n), C(n);
+    std::vector<int32_t> anc(n);
+    const float y[2] = {101.f, 99.f}, none[2] = {0.f, 0.f};
+    float m = 0.f;
+    for (int mk = 0; mk < 3; ++mk) {
+      const uint64_t W = hc_gp_filter_step(1, x.data(), n, ths[1], 0.1f, y, masks[mk], 1.f, nn.data(), 0x654321u,
+                                           xo.data(), q.data(), anc.data(), C.data(), &m);
+      uint64_t top = 0;
+      for (int i = 0; i < n; ++i) {
+        top = std::max(top, q[i]);
+        if (i % 4 == 1 && q[i] != 0) { std::printf("gp: a dead particle has weight\n"); ++bad; }
+        if (anc[i] < 0 || anc[i] >= n || q[anc[i]] == 0 || !std::isfinite(xo[2 * i]) || !std::isfinite(xo[2 * i + 1])) {
+          std::printf("gp: slot %d ancestor %d\n", i, anc[i]);
+          ++bad;
+        }
+      }
+      if (W == 0 || top != (1ull << 40) || !std::isfinite(m)) { std::printf("gp: step mask %d\n", mk); ++bad; }
+    }
+    // unobserved: sim::advance, slot for slot
+    hc_gp_filter_step(1, x.data(), n, ths[1], 0.1f, y, none, 1.f, nn.data(), 0u, xo.data(), q.data(), anc.data(),
+                      C.data(), &m);
+    for (int i = 0; i < n; ++i) {
+      float xp[2], xe[2];
+      hc_sim_path(1, &x[2 * i], ths[1], 0.1f, 0.f, 1, &nn[2 * i], xp, nullptr, xe);
+      if (std::memcmp(xe, &xo[2 * i], 8) != 0 && !(std::isnan(xe[0]) && std::isnan(xo[2 * i]))) {
+        std::printf("gp: unobserved step %d\n", i);
+        ++bad;
+      }
+    }
+    for (int i = 0; i < n; ++i) x[2 * i + 1] = -2.f;  // no live particle
+    if (hc_gp_filter_step(1, x.data(), n, ths[1], 0.1f, y, masks[0], 1.f, nn.data(), 9u, xo.data(), q.data(),
+                          anc.data(), C.data(), &m) != 0 || !std::isnan(xo[0]) || !std::isnan(xo[2 * n - 1])) {
+      std::printf("gp: no live particle\n");
+      ++bad;
+    }
+  }
+  return bad;
+}
+
 }  // namespace
 
 int main() {
@@ -557,6 +699,7 @@ int main() {
   bad += check_philox();
   bad += check_pf();
   bad += check_ps();
+  bad += check_gp();
   bad += check_colkey();
   bad += check_select();
   for (int which = 0; which < 8; ++which) {

@@ -24,13 +24,25 @@
 // steps of 2048 values would need 256 KiB, more than the CU's LDS.  LDS per block = 4 S N DEPTH (tile) + 8 N (C)
 // + 4 S N (gather) + 8 DEPTH (ll_inc, ess) + 320 (wave partials): at most 147,904 bytes (LV / FHN, N = 1024) of
 // the 160 KiB a block may declare (vissm_particle_filter_lds_bytes).
+//
+// The fully adapted filter (vissm_particle_filter_adapted; gp_math.hpp) is the same body with PROPOSAL = kAdapted:
+// geometry, stream, tile, integer pipeline, outputs and chaining are the bootstrap's, and an unobserved step is
+// sim::advance, bitwise.  At an observed step each lane scores its *pre-step* state on the predictive p(y_t | x_t-1)
+// (gp::state_logw), the block resamples behind the same four barriers, and slot j gathers ancestor a_j's pre-step
+// state (S words; mu and Sigma are recomputed rather than staged, five more words per particle that the LV / FHN
+// N = 1024 block's LDS does not have) and draws x' from p(x_t | x_t-1, y_t) of that state with its own normals
+// (gp::advance, with the death rule).  The cloud then holds the post-propagation particles, an equally weighted
+// sample of p(x_t | y_1:t); an LV draw may leave the orthant after the resampling, so unlike the bootstrap's cloud
+// it may hold NaN particles at observed steps.  They get q = 0 at the next observed step.
 #include "common.hpp"
+#include "gp_math.hpp"
 #include "pf_math.hpp"
 
 namespace vissm {
 namespace pfk {
 
 constexpr int kTileBytes = 128 * 1024;
+constexpr int kBootstrap = 0, kAdapted = 1;  // PROPOSAL
 
 constexpr int tile_depth(int S, int N) {
   const int d = kTileBytes / (4 * S * N);
@@ -59,7 +71,7 @@ __device__ __forceinline__ uint64_t wave_scan(uint64_t v, int lane) {
   return v;
 }
 
-template <int MODEL, int N>
+template <int MODEL, int N, int PROPOSAL>
 __global__ __launch_bounds__(N) void particle_filter_kernel(
     uint64_t seed, uint64_t row0, int H, int t0, int T_total, float dt, float obs_std, const float* __restrict__ theta,
     const float* __restrict__ x_start, const float* __restrict__ obs, const float* __restrict__ obs_bin,
@@ -121,7 +133,7 @@ __global__ __launch_bounds__(N) void particle_filter_kernel(
         n[0] = qd == 0 ? cur[0] : qd == 1 ? cur[1] : qd == 2 ? cur[2] : cur[3];
         n[1] = 0.f;
       }
-      sim::advance<MODEL>(x, par, n, 0.f, nullptr);
+      if constexpr (PROPOSAL == kBootstrap) sim::advance<MODEL>(x, par, n, 0.f, nullptr);
 
       // every thread reads the same addresses: block-uniform
       float yv[S], bv[S];
@@ -132,13 +144,18 @@ __global__ __launch_bounds__(N) void particle_filter_kernel(
         yv[d] = obs[static_cast<size_t>(d) * T_total + ta];
         observed = observed || bv[d] != 0.f;
       }
+      if constexpr (PROPOSAL == kAdapted) {  // an observed step moves after the resampling
+        if (!observed) sim::advance<MODEL>(x, par, n, 0.f, nullptr);
+      }
 
       float inc = dead ? sim::quiet_nan() : 0.f, es = dead ? sim::quiet_nan() : static_cast<float>(N);
       uint64_t q = 0;
       int anc = tid;
       if (observed) {
         const bool ok = sim::alive(MODEL, x);
-        const float lw = ok ? pf::obs_logw(S, x, yv, bv, obs_std) : -INFINITY;
+        float lw;
+        if constexpr (PROPOSAL == kBootstrap) lw = ok ? pf::obs_logw(S, x, yv, bv, obs_std) : -INFINITY;
+        else lw = ok ? gp::state_logw<MODEL>(x, par, yv, bv, obs_std * obs_std) : -INFINITY;
         const float wm = wave_max(lw);
         if (lane == 0) wmax[wid] = wm;
 #pragma unroll
@@ -170,6 +187,7 @@ __global__ __launch_bounds__(N) void particle_filter_kernel(
           anc = min(anc, N - 1);  // tau < W = C[N - 1]: never taken
 #pragma unroll
           for (int d = 0; d < S; ++d) x[d] = xs[d * N + anc];
+          if constexpr (PROPOSAL == kAdapted) gp::advance<MODEL>(x, par, yv, bv, obs_std * obs_std, n);
           const double li = pf::ll_increment(m, W, N);
           ll += li;
           inc = static_cast<float>(li);
@@ -238,25 +256,32 @@ struct Args {
   uint64_t* q_trace;
   int32_t* anc_trace;
   hipStream_t st;
+  int proposal;
 };
 
-template <int MODEL, int N>
+template <int MODEL, int N, int PROPOSAL>
 void launch(const Args& a) {
-  hipLaunchKernelGGL((particle_filter_kernel<MODEL, N>), dim3(a.d->K), dim3(N), 0, a.st, a.seed, a.row0, a.d->H,
-                     a.d->t0, a.d->T_total, a.d->dt, a.d->obs_std, a.theta, a.x_start, a.obs, a.obs_bin, a.loglik_in,
-                     a.loglik, a.ll_inc, a.ess, a.state_end, a.cloud,
+  hipLaunchKernelGGL((particle_filter_kernel<MODEL, N, PROPOSAL>), dim3(a.d->K), dim3(N), 0, a.st, a.seed, a.row0,
+                     a.d->H, a.d->t0, a.d->T_total, a.d->dt, a.d->obs_std, a.theta, a.x_start, a.obs, a.obs_bin,
+                     a.loglik_in, a.loglik, a.ll_inc, a.ess, a.state_end, a.cloud,
                      reinterpret_cast<unsigned long long*>(a.q_trace), a.anc_trace);
 }
 
-template <int MODEL>
+template <int MODEL, int PROPOSAL>
 void launch_n(const Args& a) {
   switch (a.d->N) {
-    case 64: launch<MODEL, 64>(a); break;
-    case 128: launch<MODEL, 128>(a); break;
-    case 256: launch<MODEL, 256>(a); break;
-    case 512: launch<MODEL, 512>(a); break;
-    default: launch<MODEL, 1024>(a); break;
+    case 64: launch<MODEL, 64, PROPOSAL>(a); break;
+    case 128: launch<MODEL, 128, PROPOSAL>(a); break;
+    case 256: launch<MODEL, 256, PROPOSAL>(a); break;
+    case 512: launch<MODEL, 512, PROPOSAL>(a); break;
+    default: launch<MODEL, 1024, PROPOSAL>(a); break;
   }
+}
+
+template <int MODEL>
+void launch_p(const Args& a) {
+  if (a.proposal == kAdapted) launch_n<MODEL, kAdapted>(a);
+  else launch_n<MODEL, kBootstrap>(a);
 }
 
 }  // namespace pfk
@@ -271,11 +296,12 @@ extern "C" int32_t vissm_particle_filter_lds_bytes(int32_t model, int32_t N) {
   return 4 * S * N * D + 8 * N + 4 * S * N + 8 * D + 16 * (4 + 8 + 8);
 }
 
-extern "C" int vissm_particle_filter(const VissmPfDesc* d, uint64_t seed, uint64_t row0, const float* theta,
-                                     const float* x_start, const float* obs, const float* obs_bin,
-                                     const double* loglik_in, double* loglik, float* ll_inc, float* ess,
-                                     float* state_end, float* cloud, uint64_t* q_trace, int32_t* anc_trace,
-                                     void* stream) {
+namespace {
+
+int run_filter(int proposal, const VissmPfDesc* d, uint64_t seed, uint64_t row0, const float* theta,
+               const float* x_start, const float* obs, const float* obs_bin, const double* loglik_in, double* loglik,
+               float* ll_inc, float* ess, float* state_end, float* cloud, uint64_t* q_trace, int32_t* anc_trace,
+               void* stream) {
   // host arithmetic only, before any GPU call
   VISSM_CHECK_ARG(d, "particle_filter: null descriptor");
   VISSM_CHECK_ARG(d->model != VISSM_MODEL_SV,
@@ -292,16 +318,45 @@ extern "C" int vissm_particle_filter(const VissmPfDesc* d, uint64_t seed, uint64
                   "particle_filter: steps %d .. %d leave the %d observations", d->t0, d->t0 + d->H, d->T_total);
   VISSM_CHECK_ARG(static_cast<int64_t>(d->K) * d->N < (int64_t{1} << 31), "particle_filter: K N = %d %d reaches 2^31",
                   d->K, d->N);
+  // (the conditional degenerates at obs_std = 0; a NaN fails the first comparison, an infinity the second)
+  VISSM_CHECK_ARG(proposal != kAdapted || (d->obs_std > 0.f && d->obs_std <= 3.4028234e38f),
+                  "particle_filter: the adapted proposal needs a positive, finite obs_std, got %g",
+                  static_cast<double>(d->obs_std));
   VISSM_CHECK_ARG(theta && x_start && loglik && state_end, "particle_filter: null pointer");
   VISSM_CHECK_ARG(d->H == 0 || (obs && obs_bin && ll_inc && ess), "particle_filter: null pointer (H > 0)");
   if (d->K == 0) return VISSM_OK;
   const Args a{d, seed, row0, theta, x_start, obs, obs_bin, loglik_in, loglik, ll_inc, ess, state_end, cloud, q_trace,
-               anc_trace, as_stream(stream)};
+               anc_trace, as_stream(stream), proposal};
   switch (d->model) {
-    case VISSM_MODEL_AR: launch_n<VISSM_MODEL_AR>(a); break;
-    case VISSM_MODEL_LV: launch_n<VISSM_MODEL_LV>(a); break;
-    default: launch_n<VISSM_MODEL_FHN>(a); break;
+    case VISSM_MODEL_AR: launch_p<VISSM_MODEL_AR>(a); break;
+    case VISSM_MODEL_LV: launch_p<VISSM_MODEL_LV>(a); break;
+    default: launch_p<VISSM_MODEL_FHN>(a); break;
   }
-  VISSM_CHECK_LAUNCH("particle_filter");
+  VISSM_CHECK_LAUNCH(proposal == kAdapted ? "particle_filter_adapted" : "particle_filter");
   return VISSM_OK;
+}
+
+}  // namespace
+
+extern "C" int vissm_particle_filter(const VissmPfDesc* d, uint64_t seed, uint64_t row0, const float* theta,
+                                     const float* x_start, const float* obs, const float* obs_bin,
+                                     const double* loglik_in, double* loglik, float* ll_inc, float* ess,
+                                     float* state_end, float* cloud, uint64_t* q_trace, int32_t* anc_trace,
+                                     void* stream) {
+  return run_filter(kBootstrap, d, seed, row0, theta, x_start, obs, obs_bin, loglik_in, loglik, ll_inc, ess, state_end,
+                    cloud, q_trace, anc_trace, stream);
+}
+
+// the adapted filter declares the bootstrap kernel's arrays: the same LDS
+extern "C" int32_t vissm_particle_filter_adapted_lds_bytes(int32_t model, int32_t N) {
+  return vissm_particle_filter_lds_bytes(model, N);
+}
+
+extern "C" int vissm_particle_filter_adapted(const VissmPfDesc* d, uint64_t seed, uint64_t row0, const float* theta,
+                                             const float* x_start, const float* obs, const float* obs_bin,
+                                             const double* loglik_in, double* loglik, float* ll_inc, float* ess,
+                                             float* state_end, float* cloud, uint64_t* q_trace, int32_t* anc_trace,
+                                             void* stream) {
+  return run_filter(kAdapted, d, seed, row0, theta, x_start, obs, obs_bin, loglik_in, loglik, ll_inc, ess, state_end,
+                    cloud, q_trace, anc_trace, stream);
 }

@@ -966,8 +966,11 @@ def sde_simulate(model_id: int, theta: torch.Tensor, x_start: torch.Tensor, H: i
 
 
 # ---------------------------------------------------------------------------------------
-# bootstrap particle filter (log-evidence and filtering bands)
+# particle filter, bootstrap or fully adapted proposal (log-evidence and filtering bands)
 # ---------------------------------------------------------------------------------------
+PF_PROPOSALS = ("bootstrap", "adapted")
+
+
 @dataclass
 class ParticleFilterResult:
     loglik: torch.Tensor                 # [K] float64: loglik_in + the increments (-inf: a dead filter)
@@ -975,6 +978,7 @@ class ParticleFilterResult:
     ess: torch.Tensor                    # [K, H] fp32, N at unobserved steps
     state_end: torch.Tensor              # [K N, S]
     cloud: Optional[torch.Tensor]        # [K N, S, H] post-resampling particles, or None
+    #                                      (adapted: post-propagation; may hold NaN particles at observed LV steps)
     q_trace: Optional[torch.Tensor]      # [K, H, N] int64 (the kernel's uint64 weights, below 2^41), or None
     anc_trace: Optional[torch.Tensor]    # [K, H, N] int32, or None
 
@@ -982,14 +986,23 @@ class ParticleFilterResult:
 def particle_filter(model_id: int, theta: torch.Tensor, x_start: torch.Tensor, obs: torch.Tensor,
                     obs_bin: torch.Tensor, dt: float, obs_std: float, N: int, seed: int, row0: int, t0: int = 0,
                     loglik_in: Optional[torch.Tensor] = None, cloud: bool = True, trace: bool = False,
-                    H: Optional[int] = None) -> ParticleFilterResult:
+                    H: Optional[int] = None, proposal: str = "bootstrap") -> ParticleFilterResult:
     """K bootstrap particle filters of N particles each, one per row of theta [K, P] (raw, as the ELBO takes it), over
     steps t0 .. t0 + H - 1 of obs / obs_bin [S, T_total] (H = T_total - t0 by default); vissm_particle_filter: one
     block per filter, one particle per lane, integer systematic resampling.  x_start: [K N, S], or [S] for every
     particle.  Observation t scores the state after transition t.  Particle (k, i) consumes the normals
     sde_simulate gives row row0 + k N + i under the same seed, so with obs_bin = 0 the cloud is that call's x.  A
     call with t0 > 0, x_start = the previous call's state_end and loglik_in = its loglik continues bitwise.  AR, LV
-    and FHN; SV has no observation model and is refused."""
+    and FHN; SV has no observation model and is refused.
+
+    proposal = "adapted" runs the fully adapted auxiliary filter instead (vissm_particle_filter_adapted): at an
+    observed step a particle is weighted on the predictive p(y_t | x_t-1) before it moves, and after the resampling
+    drawn from p(x_t | x_t-1, y_t) with its own normals.  Same rows, streams, outputs and chaining; a much lower
+    variance of loglik where obs_std is small against the process noise.  obs_std > 0 and finite."""
+    if proposal not in PF_PROPOSALS:
+        raise _lib.VissmError(f"particle_filter: proposal {proposal!r}, one of {PF_PROPOSALS} expected")
+    if proposal == "adapted" and not 0.0 < float(obs_std) < float("inf"):
+        raise _lib.VissmError(f"particle_filter: the adapted proposal needs a positive, finite obs_std, got {obs_std}")
     if model_id not in _lib.MODEL_S:
         raise _lib.VissmError(f"particle_filter: unknown model {model_id}")
     if model_id == _lib.MODEL_SV:
@@ -1039,11 +1052,11 @@ def particle_filter(model_id: int, theta: torch.Tensor, x_start: torch.Tensor, o
     if K == 0:
         return ParticleFilterResult(loglik, ll_inc, ess, state_end, cl, qt, at)
     d = _lib.PfDesc(model_id, K, N, H, t0, T_total, float(dt), float(obs_std))
-    check(_lib.load().vissm_particle_filter(ctypes.byref(d), ctypes.c_uint64(seed & (2 ** 64 - 1)),
-                                            ctypes.c_uint64(int(row0)), ptr(theta), ptr(x_start), ptr(obs),
-                                            ptr(obs_bin), ptr(loglik_in), ptr(loglik), ptr(ll_inc), ptr(ess),
-                                            ptr(state_end), ptr(cl), ptr(qt), ptr(at), _lib.stream_handle(dev)),
-          "vissm_particle_filter")
+    name = "vissm_particle_filter_adapted" if proposal == "adapted" else "vissm_particle_filter"
+    check(getattr(_lib.load(), name)(ctypes.byref(d), ctypes.c_uint64(seed & (2 ** 64 - 1)),
+                                     ctypes.c_uint64(int(row0)), ptr(theta), ptr(x_start), ptr(obs), ptr(obs_bin),
+                                     ptr(loglik_in), ptr(loglik), ptr(ll_inc), ptr(ess), ptr(state_end), ptr(cl),
+                                     ptr(qt), ptr(at), _lib.stream_handle(dev)), name)
     return ParticleFilterResult(loglik, ll_inc, ess, state_end, cl, qt, at)
 
 

@@ -702,7 +702,7 @@ class VISSMBase:
 
     @torch.no_grad()
     def particle_filter(self, n_theta: int = 64, n_particles: int = 1024, probs=DEFAULT_PROBS,
-                        chunk: Optional[int] = None) -> Dict[str, np.ndarray]:
+                        chunk: Optional[int] = None, proposal: str = "bootstrap") -> Dict[str, np.ndarray]:
         """A check of the fitted posterior that does not come out of the flows: K = n_theta bootstrap particle filters
         of N = n_particles particles each (ops.particle_filter), one per theta sample, over the model's observations
         from its x0.  theta = global samples 0 .. K - 1 of the first window's draw posterior_summary uses (same
@@ -716,15 +716,24 @@ class VISSMBase:
         from q(theta), so this is the filtering distribution averaged over q(theta).  T = min(target_len(), the
         observations' length).  Philox key seed ^ FILTER_SEED_XOR, rows global_step K N + k N + i; `chunk` steps per
         launch (default filter_chunk()), chained through the end state and the running log-likelihood, change
-        nothing.  SV has no observation model: ValueError."""
-        return self._filter_pass(n_theta, n_particles, probs, chunk, None)[0]
+        nothing.  SV has no observation model: ValueError.
 
-    def _filter_pass(self, n_theta, n_particles, probs, chunk, keep):
+        proposal = "adapted" runs the fully adapted filter (ops.particle_filter(proposal="adapted")) on the same
+        theta rows, key, rows and chunks: a much lower variance of filter/loglik where obs_std is small against the
+        process noise.  The result then also carries filter/proposal = "adapted", and its bands summarise the
+        post-propagation particles (n_valid leaves out the LV particles that left the orthant after a resampling).
+        With the default every launch and every entry is the bootstrap filter's, with no new key.  Any other value:
+        VissmError."""
+        return self._filter_pass(n_theta, n_particles, probs, chunk, None, proposal)[0]
+
+    def _filter_pass(self, n_theta, n_particles, probs, chunk, keep, proposal="bootstrap"):
         """particle_filter()'s launches and result; with keep = (M, cap) the arguments of particle_smoother() are
         checked before the first launch and every chunk's cloud stays on the device: (res, theta, [(t0, cloud)])."""
         from . import ops
         md = self.mdef
         what = "particle_filter" if keep is None else "particle_smoother"
+        if proposal not in ops.PF_PROPOSALS:
+            raise _lib.VissmError(f"{what}: proposal {proposal!r}, one of {ops.PF_PROPOSALS} expected")
         if md.model_id == _lib.MODEL_SV or getattr(self, "filter_data", None) is None:
             raise ValueError(f"{what}: SV has no observation model (its first coordinate is the observed "
                              "series)")
@@ -768,7 +777,7 @@ class VISSMBase:
         for t0 in range(0, T, chunk):
             m = min(chunk, T - t0)
             r = ops.particle_filter(md.model_id, th, state, obs, obs_bin, md.dt, md.obs_std, N, seed, row0, t0=t0,
-                                    loglik_in=ll, cloud=True, H=m)
+                                    loglik_in=ll, cloud=True, H=m, proposal=proposal)
             state, ll = r.state_end, r.loglik
             incs.append(r.ll_inc)
             esss.append(r.ess)
@@ -776,6 +785,8 @@ class VISSMBase:
             if keep is not None:
                 clouds.append((t0, r.cloud))
         res: Dict[str, np.ndarray] = {"probs": p, "filter/theta": th.cpu().numpy()}
+        if proposal != "bootstrap":
+            res["filter/proposal"] = np.asarray(proposal)
         res["filter/loglik"] = ll.cpu().numpy() if ll is not None else np.zeros(K)
         res["filter/ll_inc"] = torch.cat(incs + [torch.zeros(K, 0, device=dev)], 1).cpu().numpy()
         res["filter/ess"] = torch.cat(esss + [torch.zeros(K, 0, device=dev)], 1).cpu().numpy()
@@ -787,9 +798,9 @@ class VISSMBase:
         return res, th, clouds
 
     def save_filter(self, PATH: str, n_theta: int = 64, n_particles: int = 1024, probs=DEFAULT_PROBS,
-                    chunk: Optional[int] = None) -> Dict[str, np.ndarray]:
+                    chunk: Optional[int] = None, proposal: str = "bootstrap") -> Dict[str, np.ndarray]:
         """particle_filter written as one .npz by rank 0 (every rank computes the same result)."""
-        res = self.particle_filter(n_theta, n_particles, probs, chunk)
+        res = self.particle_filter(n_theta, n_particles, probs, chunk, proposal)
         if self.dist.rank == 0:
             d = os.path.dirname(PATH)
             if d:
@@ -801,7 +812,7 @@ class VISSMBase:
     # ------------------------------------------------------------------ particle smoother
     @torch.no_grad()
     def particle_smoother(self, n_theta: int = 64, n_particles: int = 1024, n_paths: int = 64, probs=DEFAULT_PROBS,
-                          chunk: Optional[int] = None) -> Dict[str, np.ndarray]:
+                          chunk: Optional[int] = None, proposal: str = "bootstrap") -> Dict[str, np.ndarray]:
         """The check that is comparable with what the engine fits: the variational posterior over the latent path is
         a smoothing distribution p(x_t | y_1:T), the filter's bands are filtering distributions p(x_t | y_1:t).
         Forward filtering, then backward simulation (ops.particle_smooth): the forward pass is particle_filter()'s,
@@ -815,11 +826,14 @@ class VISSMBase:
         smooth/quantiles [Q, S, T], the column summary of the K M trajectories of each step: the smoothing
         distribution averaged over q(theta), to lay over paths/quantiles of posterior_summary().  A filter that died
         contributes NaN trajectories, which n_valid leaves out.  `chunk` changes nothing; every rank runs the same
-        launches and holds the same result.  SV has no observation model: ValueError."""
+        launches and holds the same result.  SV has no observation model: ValueError.
+
+        proposal = "adapted": the forward pass is particle_filter(proposal="adapted")'s, whose cloud is, like the
+        bootstrap's, an equally weighted sample of each filtering law; the backward pass is untouched."""
         from . import ops
         md = self.mdef
         K, N, M = int(n_theta), int(n_particles), int(n_paths)
-        res, th, clouds = self._filter_pass(K, N, probs, chunk, (M, SMOOTH_CLOUD_BYTES))
+        res, th, clouds = self._filter_pass(K, N, probs, chunk, (M, SMOOTH_CLOUD_BYTES), proposal)
         S, Q = _lib.MODEL_S[md.model_id], res["probs"].size
         seed = self.engine.seed ^ SMOOTH_SEED_XOR
         row0 = self.global_step * K * N
@@ -838,9 +852,10 @@ class VISSMBase:
         return res
 
     def save_smoother(self, PATH: str, n_theta: int = 64, n_particles: int = 1024, n_paths: int = 64,
-                      probs=DEFAULT_PROBS, chunk: Optional[int] = None) -> Dict[str, np.ndarray]:
+                      probs=DEFAULT_PROBS, chunk: Optional[int] = None,
+                      proposal: str = "bootstrap") -> Dict[str, np.ndarray]:
         """particle_smoother written as one .npz by rank 0 (every rank computes the same result)."""
-        res = self.particle_smoother(n_theta, n_particles, n_paths, probs, chunk)
+        res = self.particle_smoother(n_theta, n_particles, n_paths, probs, chunk, proposal)
         if self.dist.rank == 0:
             d = os.path.dirname(PATH)
             if d:
