@@ -116,6 +116,41 @@ def build_model(family: str, B: int, M: int, k: int, n_flows: int, H: int, n_lay
     return model
 
 
+def pin_theta(model, target):
+    """Put q(theta) at `target` (raw theta, e.g. sim_util.TRUE_THETA of the data's generator) and return the model.  A
+    random draw's LV rates send every particle or trajectory out of the positive orthant at its first step, and a
+    random AR theta_1 above 1 sends the particles so far from the data that no weight is left.  The last bijector's
+    output is (z - shift) e^-ls, so a log-scale bias of 3 and a shift bias of -e^3 target give
+    theta = target + e^-3 (z - ...)."""
+    vals = model.store.state_numpy()
+    name = f"theta/maf{model.mdef.n_maf - 1}/dense3/bias"
+    bias = vals[name].copy()
+    bias[0::2] = -np.exp(3.0) * np.asarray(target)
+    bias[1::2] = 3.0
+    vals[name] = bias
+    model.store.load_numpy(vals)
+    return model
+
+
+# The product cases of the filter, smoother and adapted-filter tests: family -> (B, M, k, n_flows, H, n_layers, fw), T,
+# precision, S (the shapes of tests/test_gpu_forecast.py), the filters and particles of the two filter tests, and the
+# result's keys.
+FILTER_CASES = {"ar": ((64, 30, 5, 2, 20, 3, 4), 150, 0, 1),
+                "lv": ((32, 24, 4, 2, 16, 5, 3), 24, 1, 2)}
+FILTER_KF, FILTER_NF = 8, 64
+FILTER_KEYS = ("probs", "filter/loglik", "filter/theta", "filter/ll_inc", "filter/ess", "filter/mean", "filter/sd",
+               "filter/n_valid", "filter/quantiles")
+SMOOTH_KEYS = ("smooth/mean", "smooth/sd", "smooth/n_valid", "smooth/quantiles")
+
+
+def filter_model(family: str, device: str = "cuda:0"):
+    """The FILTER_CASES model of the family with q(theta) at its generator's parameters."""
+    from tests.sim_util import TRUE_THETA
+    shape, T, prec, _ = FILTER_CASES[family]
+    model = build_model(family, *shape, device, T=T, precision=prec, seed=3)
+    return pin_theta(model, TRUE_THETA[model.mdef.model_id])
+
+
 FAMILY_SHAPE = {  # D (state dimension), n_hidden, BN, stride-2 interleaved head (SURVEY.md §8a)
     "ar": (1, 1, False, False), "sv": (1, 3, True, False), "lv": (2, 3, True, True), "fhn": (2, 3, True, True)}
 

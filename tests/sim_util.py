@@ -82,3 +82,78 @@ def replay(model, x_start, th, dt, normals, H, obs_std=None, dtype=np.float64):
         if ys is not None:
             ys[:, :, t] = x + dtype(obs_std) * nn[:, t, S:]
     return xs, ys, x, prev, raw, exit_step
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# inputs, bit comparisons and bars shared by the particle filter tests (tests/test_gpu_particle.py,
+# tests/test_gpu_adapted.py)
+# ----------------------------------------------------------------------------------------------------------------
+PF_SEED = 0x9F17E2
+PF_OBS_STD = {AR: 1.0, LV: 1.0, FHN: 0.1}
+PF_ONE = 1 << 40
+
+
+def filter_inputs(model, K, N, rng):
+    """theta [K, P] within 10 % of the generators' true values (AR theta_1 in [0.5, 0.95]) and start states [K N, S]
+    within 10 % of theirs: tests/test_gpu_simulate.py's stable range."""
+    P, S = P_OF[model], S_OF[model]
+    true = np.asarray(TRUE_THETA[model])
+    if model == AR:
+        th = true * rng.uniform(0.9, 1.1, (K, P))
+        th[:, 1] = rng.uniform(0.5, 0.95, K)
+    elif model == LV:
+        th = true + np.log(rng.uniform(0.9, 1.1, (K, P)))
+    else:
+        th = true * rng.uniform(0.9, 1.1, (K, P))
+    x0 = np.asarray(TRUE_X[model]) * rng.uniform(0.9, 1.1, (K * N, S))
+    return th.astype(np.float32), x0.astype(np.float32)
+
+
+def filter_series(model, T, pattern, rng):
+    """One float64 path from the true start at the true theta, observed with N(x, obs_std) noise -- "all": every
+    coordinate at every step; "tenth": every coordinate at steps 9, 19, ..; "coord": the first coordinate only, at
+    steps 2, 5, ..; "none": nothing.  Unobserved entries hold -1, as the data files do."""
+    S = S_OF[model]
+    th = np.asarray(TRUE_THETA[model], np.float64)
+    x = np.asarray(TRUE_X[model], np.float64)
+    path = np.zeros((S, T))
+    for t in range(T):
+        x = step(model, x, th, DT[model], rng.standard_normal(S))
+        path[:, t] = x
+    assert alive(model, path.T).all()
+    b = np.zeros((S, T), np.float32)
+    if pattern == "all":
+        b[:] = 1.0
+    elif pattern == "tenth":
+        b[:, 9::10] = 1.0
+    elif pattern == "coord":
+        b[0, 2::3] = 1.0
+    y = np.where(b > 0, path + PF_OBS_STD[model] * rng.standard_normal((S, T)), -1.0).astype(np.float32)
+    return y, b
+
+
+def bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.int64 if a.dtype.itemsize == 8 else np.int32)
+
+
+def same_bits(a, b, keys=("loglik", "ll_inc", "ess", "state_end", "cloud", "q", "anc")):
+    for k in keys:
+        assert (a[k] is None) == (b[k] is None), k
+        if a[k] is not None:
+            assert np.array_equal(bits(a[k]), bits(b[k])), k
+
+
+def state_bar(ref64, ref32):
+    """tests/test_gpu_simulate.py's bar: 8 * max(e32, 2^-20 * column mean |ref64|) per column [S, H], and e32."""
+    both = np.isfinite(ref64) & np.isfinite(ref32)
+    e32 = float(np.max(np.abs(ref32.astype(np.float64) - ref64)[both])) if both.any() else 0.0
+    with np.errstate(invalid="ignore"):
+        scale = np.nan_to_num(np.nanmean(np.abs(ref64), axis=0), nan=0.0)
+    return 8.0 * np.maximum(e32, 2.0 ** -20 * scale), e32
+
+
+def resample_u(seed, t, r):
+    from tests import philox_ref
+    w = philox_ref.philox4x32_10([t, 1, r & 0xFFFFFFFF, r >> 32], [seed & 0xFFFFFFFF, seed >> 32])
+    return int(w[0]) >> 8

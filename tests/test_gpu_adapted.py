@@ -20,8 +20,11 @@ from tests import gpf_ref as GR
 from tests import pf_ref as PR
 from tests import ps_ref as PS
 from tests import sim_util as SU
-from tests.test_gpu_particle import (CASES, KEYS, KF, NF, OBS_STD, ONE, SEED, _bar, _bits, _inputs, _model,
-                                     _resample_u, _same, _series)
+from tests.parity_util import (FILTER_CASES as CASES, FILTER_KEYS as KEYS, FILTER_KF as KF, FILTER_NF as NF,
+                               filter_model as _model)
+from tests.sim_util import (PF_OBS_STD as OBS_STD, PF_ONE as ONE, PF_SEED as SEED, filter_inputs as _inputs,
+                            filter_series as _series, resample_u as _resample_u, same_bits as _same, state_bar as _bar,
+                            bits as _bits)
 
 pytestmark = pytest.mark.gpu
 

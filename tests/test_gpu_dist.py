@@ -8,15 +8,11 @@ order), the parameters after clip + Adamax are bitwise identical on both ranks, 
 overlapped reduce equals the single blocking all-reduce bitwise.  AR at fp32 (two windows) and LV at bf16 (one
 window: the two-sample three-layer backward and the split-bf16 window-shared GEMMs, whose dC inputs are the
 rank-local sums)."""
-import os
-import queue
-import socket
-import time
-
 import numpy as np
 import pytest
 import torch
-import torch.multiprocessing as mp
+
+from tests.dist_util import attach, run_ranks
 
 pytestmark = pytest.mark.gpu
 
@@ -26,68 +22,29 @@ CASES = {"ar": ((P, 30, 5, 2, 20, 3, 4), 150, 0, 1e-5),
          "lv": ((P, 24, 4, 2, 16, 5, 3), 24, 1, 1e-4)}
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
 def _model(family="ar"):
     from tests.parity_util import build_model
     (B, M, k, nf, H, nl, fw), T, prec, _ = CASES[family]
     return build_model(family, B, M, k, nf, H, nl, fw, "cuda:0", T=T, precision=prec, seed=3)
 
 
-def _worker(rank, world, port, overlap, family, out, shared=True):
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    torch.cuda.set_device(0)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    from viforssms_amd.vi_ssm import DistCtx
-    model = _model(family)
-    model.dist = DistCtx(rank, world)
-    model.p_local = P // world
+def _worker(rank, world, overlap, family, shared=True):
+    model = attach(_model(family), rank, world, P)
     model.overlap_allreduce = overlap
     model.shared_dc_allreduce = shared
     np.random.seed(SEED)
     starts = model.select_windows()
     o = model.elbo_step(model.batch_for(starts), 0)
     torch.cuda.synchronize()
-    out.put((rank, overlap, starts, model.store.grad.cpu().numpy(), model.store.flat.cpu().numpy(),
-             o["elbo"].cpu().numpy(), float(o["global_norm"][0]), model.last_allreduce_bytes))
-    dist.barrier()
-    dist.destroy_process_group()
-
-
-def _run(overlap, family, shared=True):
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, overlap, family, q, shared)) for r in range(2)]
-    for p in procs:
-        p.start()
-    res = {}
-    deadline = time.time() + 240
-    while len(res) < 2:
-        try:
-            r = q.get(timeout=1)
-            res[r[0]] = r
-        except queue.Empty:
-            assert not any(p.exitcode not in (None, 0) for p in procs), "a rank failed"
-            assert time.time() < deadline, "timed out"
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
-    return res
+    return (rank, overlap, starts, model.store.grad.cpu().numpy(), model.store.flat.cpu().numpy(),
+            o["elbo"].cpu().numpy(), float(o["global_norm"][0]), model.last_allreduce_bytes)
 
 
 @pytest.mark.parametrize("family", ["ar", "lv"])
 def test_two_rank_hip_gradient_equals_full_batch_and_params_agree(family):
     gtol = CASES[family][3]
-    ov = _run(True, family)
-    blk = _run(False, family)
+    ov = run_ranks(_worker, args=(True, family))
+    blk = run_ranks(_worker, args=(False, family))
     # full batch, one process
     model = _model(family)
     np.random.seed(SEED)
@@ -117,8 +74,8 @@ def test_lv_window_shared_gradients_summed_through_dC():
     the window-shared backward (feature MLP, conv over the time-mixing features: lotka_volterra_partial.py:71-82)
     runs replicated on it, so those variables leave the gradient all-reduce (VISSMBase._shared_grad_plan).  Same
     gradient as all-reducing every variable (linear in dC), fewer bytes, ranks bitwise equal."""
-    via_dc = _run(True, "lv", shared=True)
-    full = _run(True, "lv", shared=False)
+    via_dc = run_ranks(_worker, args=(True, "lv", True))
+    full = run_ranks(_worker, args=(True, "lv", False))
     g_dc, g_full = via_dc[0][3], full[0][3]
     assert np.array_equal(via_dc[0][3], via_dc[1][3]) and np.array_equal(via_dc[0][4], via_dc[1][4])
     assert np.linalg.norm(g_dc - g_full) / np.linalg.norm(g_full) < 1e-4

@@ -23,22 +23,15 @@ GROUP_KEYS = ("mean", "sd", "quantiles", "n_valid")
 
 
 def _model(family):
-    from tests.parity_util import build_model
+    from tests.parity_util import build_model, pin_theta
     shape, T, prec, _ = CASES[family]
     model = build_model(family, *shape, DEV, T=T, precision=prec, seed=3)
     if family == "lv":
         # build_model's random q(theta) draws log-rates ~ N(0, 1): e^th1 ~ 1 against the generator's 0.0025, and
         # every trajectory leaves the positive orthant at its first step.  Put q(theta) where a fitted model has it:
-        # the last bijector's output is (z - shift) e^-ls, so a log-scale bias of 3 and a shift bias of
-        # -e^3 target give theta = target + e^-3 (z - ...), the generator's log-rates within a few percent.
+        # the generator's log-rates within a few percent.
         from tests.sim_util import LV, TRUE_THETA
-        vals = model.store.state_numpy()
-        name = f"theta/maf{model.mdef.n_maf - 1}/dense3/bias"
-        bias = vals[name].copy()
-        bias[0::2] = -np.exp(3.0) * np.asarray(TRUE_THETA[LV])
-        bias[1::2] = 3.0
-        vals[name] = bias
-        model.store.load_numpy(vals)
+        pin_theta(model, TRUE_THETA[LV])
     return model
 
 

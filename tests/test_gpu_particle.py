@@ -19,53 +19,16 @@ import torch
 from tests import pf_ref as PR
 from tests import philox_ref
 from tests import sim_util as SU
+from tests.parity_util import (FILTER_CASES as CASES, FILTER_KEYS as KEYS, FILTER_KF as KF, FILTER_NF as NF,
+                               filter_model as _model)
+from tests.sim_util import (PF_OBS_STD as OBS_STD, PF_ONE as ONE, PF_SEED as SEED, filter_inputs as _inputs,
+                            filter_series as _series, resample_u as _resample_u, same_bits as _same, state_bar as _bar,
+                            bits as _bits)
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SEED = 0x9F17E2
-OBS_STD = {SU.AR: 1.0, SU.LV: 1.0, SU.FHN: 0.1}
-ONE = 1 << 40
-
-
-def _inputs(model, K, N, rng):
-    """theta [K, P] within 10 % of the generators' true values (AR theta_1 in [0.5, 0.95]) and start states [K N, S]
-    within 10 % of theirs: tests/test_gpu_simulate.py's stable range."""
-    P, S = SU.P_OF[model], SU.S_OF[model]
-    true = np.asarray(SU.TRUE_THETA[model])
-    if model == SU.AR:
-        th = true * rng.uniform(0.9, 1.1, (K, P))
-        th[:, 1] = rng.uniform(0.5, 0.95, K)
-    elif model == SU.LV:
-        th = true + np.log(rng.uniform(0.9, 1.1, (K, P)))
-    else:
-        th = true * rng.uniform(0.9, 1.1, (K, P))
-    x0 = np.asarray(SU.TRUE_X[model]) * rng.uniform(0.9, 1.1, (K * N, S))
-    return th.astype(np.float32), x0.astype(np.float32)
-
-
-def _series(model, T, pattern, rng):
-    """One float64 path from the true start at the true theta, observed with N(x, obs_std) noise -- "all": every
-    coordinate at every step; "tenth": every coordinate at steps 9, 19, ..; "coord": the first coordinate only, at
-    steps 2, 5, ..; "none": nothing.  Unobserved entries hold -1, as the data files do."""
-    S = SU.S_OF[model]
-    th = np.asarray(SU.TRUE_THETA[model], np.float64)
-    x = np.asarray(SU.TRUE_X[model], np.float64)
-    path = np.zeros((S, T))
-    for t in range(T):
-        x = SU.step(model, x, th, SU.DT[model], rng.standard_normal(S))
-        path[:, t] = x
-    assert SU.alive(model, path.T).all()
-    b = np.zeros((S, T), np.float32)
-    if pattern == "all":
-        b[:] = 1.0
-    elif pattern == "tenth":
-        b[:, 9::10] = 1.0
-    elif pattern == "coord":
-        b[0, 2::3] = 1.0
-    y = np.where(b > 0, path + OBS_STD[model] * rng.standard_normal((S, T)), -1.0).astype(np.float32)
-    return y, b
 
 
 def _run(model, th, x0, obs, obs_bin, N, row0=0, t0=0, H=None, loglik_in=None, cloud=True, trace=True, seed=SEED):
@@ -80,27 +43,6 @@ def _run(model, th, x0, obs, obs_bin, N, row0=0, t0=0, H=None, loglik_in=None, c
             "cloud": c(r.cloud), "q": c(r.q_trace), "anc": c(r.anc_trace)}
 
 
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.int64 if a.dtype.itemsize == 8 else np.int32)
-
-
-def _same(a, b, keys=("loglik", "ll_inc", "ess", "state_end", "cloud", "q", "anc")):
-    for k in keys:
-        assert (a[k] is None) == (b[k] is None), k
-        if a[k] is not None:
-            assert np.array_equal(_bits(a[k]), _bits(b[k])), k
-
-
-def _bar(ref64, ref32):
-    """tests/test_gpu_simulate.py's bar: 8 * max(e32, 2^-20 * column mean |ref64|) per column [S, H], and e32."""
-    both = np.isfinite(ref64) & np.isfinite(ref32)
-    e32 = float(np.max(np.abs(ref32.astype(np.float64) - ref64)[both])) if both.any() else 0.0
-    with np.errstate(invalid="ignore"):
-        scale = np.nan_to_num(np.nanmean(np.abs(ref64), axis=0), nan=0.0)
-    return 8.0 * np.maximum(e32, 2.0 ** -20 * scale), e32
-
-
 def _logw32(x, y, b, sd):
     """pf_ref.obs_logw in numpy float32 arithmetic: what fp32 costs the log-weight."""
     f = np.float32
@@ -110,11 +52,6 @@ def _logw32(x, y, b, sd):
             z = (x[..., d].astype(f) - f(y[d])) / f(sd)
             lw = lw + f(b[d]) * (f(-0.5) * z * z - np.log(f(sd)) - f(PR.HALF_LOG_2PI))
     return lw
-
-
-def _resample_u(seed, t, r):
-    w = philox_ref.philox4x32_10([t, 1, r & 0xFFFFFFFF, r >> 32], [seed & 0xFFFFFFFF, seed >> 32])
-    return int(w[0]) >> 8
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -398,32 +335,6 @@ def test_log_evidence_agrees_with_the_reference_and_kalman():
 # ----------------------------------------------------------------------------------------------------------------
 # 6. product
 # ----------------------------------------------------------------------------------------------------------------
-# family -> (B, M, k, n_flows, H, n_layers, fw), T, precision, S: the shapes of tests/test_gpu_forecast.py
-CASES = {"ar": ((64, 30, 5, 2, 20, 3, 4), 150, 0, 1),
-         "lv": ((32, 24, 4, 2, 16, 5, 3), 24, 1, 2)}
-KF, NF = 8, 64
-KEYS = ("probs", "filter/loglik", "filter/theta", "filter/ll_inc", "filter/ess", "filter/mean", "filter/sd",
-        "filter/n_valid", "filter/quantiles")
-
-
-def _model(family):
-    from tests.parity_util import build_model
-    shape, T, prec, _ = CASES[family]
-    model = build_model(family, *shape, DEV, T=T, precision=prec, seed=3)
-    # put q(theta) at the generator's parameters, as tests/test_gpu_forecast.py does for LV: a random draw's LV rates
-    # send every particle out of the positive orthant at its first step, and a random AR theta_1 above 1 sends the
-    # particles so far from the data that no weight is left.  The last bijector's output is (z - shift) e^-ls, so a
-    # log-scale bias of 3 and a shift bias of -e^3 target give theta = target + e^-3 (z - ...).
-    vals = model.store.state_numpy()
-    name = f"theta/maf{model.mdef.n_maf - 1}/dense3/bias"
-    bias = vals[name].copy()
-    bias[0::2] = -np.exp(3.0) * np.asarray(SU.TRUE_THETA[model.mdef.model_id])
-    bias[1::2] = 3.0
-    vals[name] = bias
-    model.store.load_numpy(vals)
-    return model
-
-
 @pytest.fixture(scope="module", params=["ar", "lv"])
 def filtered(request):
     model = _model(request.param)

@@ -19,6 +19,7 @@ from tests import pf_ref as PR
 from tests import philox_ref
 from tests import ps_ref as PS
 from tests import sim_util as SU
+from tests.parity_util import FILTER_CASES as CASES, FILTER_KEYS, SMOOTH_KEYS, filter_model as _model
 
 pytestmark = pytest.mark.gpu
 
@@ -350,28 +351,7 @@ def test_smoothing_moments_agree_with_the_reference_and_rts():
 # ----------------------------------------------------------------------------------------------------------------
 # 5. product
 # ----------------------------------------------------------------------------------------------------------------
-# family -> (B, M, k, n_flows, H, n_layers, fw), T, precision, S: the shapes of tests/test_gpu_particle.py
-CASES = {"ar": ((64, 30, 5, 2, 20, 3, 4), 150, 0, 1),
-         "lv": ((32, 24, 4, 2, 16, 5, 3), 24, 1, 2)}
 KF, NF, MF = 8, 128, 64
-FILTER_KEYS = ("probs", "filter/loglik", "filter/theta", "filter/ll_inc", "filter/ess", "filter/mean", "filter/sd",
-               "filter/n_valid", "filter/quantiles")
-SMOOTH_KEYS = ("smooth/mean", "smooth/sd", "smooth/n_valid", "smooth/quantiles")
-
-
-def _model(family):
-    from tests.parity_util import build_model
-    shape, T, prec, _ = CASES[family]
-    model = build_model(family, *shape, DEV, T=T, precision=prec, seed=3)
-    # q(theta) at the generator's parameters, as tests/test_gpu_particle.py puts it: a random draw leaves no weight
-    vals = model.store.state_numpy()
-    name = f"theta/maf{model.mdef.n_maf - 1}/dense3/bias"
-    bias = vals[name].copy()
-    bias[0::2] = -np.exp(3.0) * np.asarray(SU.TRUE_THETA[model.mdef.model_id])
-    bias[1::2] = 3.0
-    vals[name] = bias
-    model.store.load_numpy(vals)
-    return model
 
 
 @pytest.fixture(scope="module", params=["ar", "lv"])
@@ -416,7 +396,7 @@ def test_product_is_the_filter_plus_the_by_hand_chain(smoothed):
 
 
 def test_product_chunking_changes_nothing_and_refusals(smoothed, monkeypatch):
-    from viforssms_amd import vi_ssm
+    from viforssms_amd import diagnostics
     family, model, got = smoothed
     for chunk in (7, 64):
         res = model.particle_smoother(KF, NF, MF, chunk=chunk)
@@ -427,11 +407,11 @@ def test_product_chunking_changes_nothing_and_refusals(smoothed, monkeypatch):
         with pytest.raises(ValueError):
             model.particle_smoother(**{**dict(n_theta=KF, n_particles=NF, n_paths=MF), **bad})
     _, T, _, S = CASES[family]
-    assert vi_ssm.SMOOTH_CLOUD_BYTES == 8 << 30
-    monkeypatch.setattr(vi_ssm, "SMOOTH_CLOUD_BYTES", 4 * KF * NF * S * T - 1)
+    assert diagnostics.SMOOTH_CLOUD_BYTES == 8 << 30
+    monkeypatch.setattr(diagnostics, "SMOOTH_CLOUD_BYTES", 4 * KF * NF * S * T - 1)
     with pytest.raises(ValueError, match="lower n_theta or n_particles"):
         model.particle_smoother(KF, NF, MF)
-    monkeypatch.setattr(vi_ssm, "SMOOTH_CLOUD_BYTES", 4 * KF * NF * S * T)
+    monkeypatch.setattr(diagnostics, "SMOOTH_CLOUD_BYTES", 4 * KF * NF * S * T)
     res = model.particle_smoother(KF, NF, MF)
     assert np.array_equal(res["smooth/mean"], got["smooth/mean"], equal_nan=True)
 

@@ -3,15 +3,10 @@ each rank a fresh child process).  The Philox rows are keyed by the global sampl
 are together the sample set of one process holding the full batch; the select's only cross-rank quantity is an
 integer histogram (SUM all-reduce), so the quantiles are bitwise equal on both ranks and equal to the single
 process's.  The means' double sums are reduced in another order: within the moments' bound."""
-import os
-import queue
-import socket
-import time
-
 import numpy as np
 import pytest
-import torch
-import torch.multiprocessing as mp
+
+from tests.dist_util import attach, run_ranks
 
 pytestmark = pytest.mark.gpu
 
@@ -22,59 +17,19 @@ KEYS = ("paths/mean", "paths/sd", "paths/quantiles", "paths/n_valid", "theta/mea
         "theta/n_valid")
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
 def _model():
     from tests.parity_util import build_model
     return build_model("ar", *SHAPE, "cuda:0", T=T, precision=0, seed=3)
 
 
-def _worker(rank, world, port, out):
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    torch.cuda.set_device(0)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    from viforssms_amd.vi_ssm import DistCtx
-    model = _model()
-    model.dist = DistCtx(rank, world)
-    model.p_local = P // world
+def _worker(rank, world):
+    model = attach(_model(), rank, world, P)
     res = model.posterior_summary(PROBS)
-    torch.cuda.synchronize()
-    out.put((rank, {k: res[k] for k in KEYS}))
-    dist.barrier()
-    dist.destroy_process_group()
-
-
-def _run():
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    res = {}
-    deadline = time.time() + 240
-    while len(res) < 2:
-        try:
-            r = q.get(timeout=1)
-            res[r[0]] = r[1]
-        except queue.Empty:
-            assert not any(p.exitcode not in (None, 0) for p in procs), "a rank failed"
-            assert time.time() < deadline, "timed out"
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
-    return res
+    return {k: res[k] for k in KEYS}
 
 
 def test_two_rank_summary_equals_full_batch():
-    res = _run()      # both children have exited (exit codes checked) before this process touches the GPU
+    res = run_ranks(_worker)      # both children have exited (exit codes checked) before this process touches the GPU
     full = _model().posterior_summary(PROBS)
     r0, r1 = res[0], res[1]
     for k in KEYS:

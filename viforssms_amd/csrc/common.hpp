@@ -52,6 +52,13 @@ __device__ __forceinline__ void box_muller4(u4 r, float (&v)[4]) {
   v[3] = r2 * __builtin_amdgcn_sinf(t2);
 }
 
+// Group g (four normals) of row `row` of the stream keyed (k0, k1): the forecast and the particle filters walk a row
+// with this one definition, so a particle consumes the normals the forecast gives the same row.
+__device__ __forceinline__ void draw4(uint32_t g, uint64_t row, uint32_t k0, uint32_t k1, float (&v)[4]) {
+  const u4 c{g, 0u, static_cast<uint32_t>(row), static_cast<uint32_t>(row >> 32)};
+  box_muller4(philox4x32_10(c, k0, k1), v);
+}
+
 // ---------------------------------------------------------------------------
 // reductions (wave64)
 // ---------------------------------------------------------------------------

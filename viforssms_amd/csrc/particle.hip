@@ -49,11 +49,6 @@ constexpr int tile_depth(int S, int N) {
   return d > 64 ? 64 : d;
 }
 
-__device__ __forceinline__ void draw4(uint32_t g, uint64_t row, uint32_t k0, uint32_t k1, float (&v)[4]) {
-  const u4 c{g, 0u, static_cast<uint32_t>(row), static_cast<uint32_t>(row >> 32)};
-  box_muller4(philox4x32_10(c, k0, k1), v);
-}
-
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));

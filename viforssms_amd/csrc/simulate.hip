@@ -21,11 +21,6 @@ namespace {
 constexpr int kTile = VISSM_SIM_TILE;
 static_assert(kTile == 64, "a tile row is one wave-wide store of 64 consecutive steps");
 
-__device__ __forceinline__ void draw4(uint32_t g, uint64_t row, uint32_t k0, uint32_t k1, float (&v)[4]) {
-  const u4 c{g, 0u, static_cast<uint32_t>(row), static_cast<uint32_t>(row >> 32)};
-  box_muller4(philox4x32_10(c, k0, k1), v);
-}
-
 // LDS writes of this wave's lanes become visible to its other lanes (DS operations of a wave complete in order)
 __device__ __forceinline__ void wave_lds_fence() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");

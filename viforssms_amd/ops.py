@@ -922,6 +922,27 @@ def col_order_stats(x: torch.Tensor, ranks: torch.Tensor, dist=None) -> torch.Te
     return out
 
 
+# argument checks shared by sde_simulate, particle_filter and particle_smooth (fn: the caller's name, for the message)
+def _sv_refused(fn: str, lacks: str) -> "_lib.VissmError":
+    return _lib.VissmError(f"{fn}: no {lacks} for SV (its first coordinate is the observed series)")
+
+
+def _model_dims(fn: str, model_id: int, sv_lacks: Optional[str] = None):
+    """(S, P) of the model; with sv_lacks (what SV does not have) SV is refused."""
+    if model_id not in _lib.MODEL_S:
+        raise _lib.VissmError(f"{fn}: unknown model {model_id}")
+    if sv_lacks is not None and model_id == _lib.MODEL_SV:
+        raise _sv_refused(fn, sv_lacks)
+    return _lib.MODEL_S[model_id], _lib.MODEL_P[model_id]
+
+
+def _key_and_row(fn: str, seed: int, row0: int):
+    """The Philox key (seed, masked to 64 bits) and first row of a launch as the C ABI takes them."""
+    if not 0 <= int(row0) < 2 ** 64:
+        raise _lib.VissmError(f"{fn}: row0={row0} outside [0, 2^64)")
+    return ctypes.c_uint64(seed & (2 ** 64 - 1)), ctypes.c_uint64(int(row0))
+
+
 # ---------------------------------------------------------------------------------------
 # forward simulation (posterior-predictive forecasts)
 # ---------------------------------------------------------------------------------------
@@ -934,9 +955,7 @@ def sde_simulate(model_id: int, theta: torch.Tensor, x_start: torch.Tensor, H: i
     NS = S (2 S with observations), so a call with t0 > 0 and x_start = an earlier call's x_end continues that
     simulation bitwise.  A dead sample (state not finite; LV: outside the positive orthant) is NaN from its dying
     step on.  H = 0: empty x / y and x_end = x_start, no launch."""
-    if model_id not in _lib.MODEL_S:
-        raise _lib.VissmError(f"sde_simulate: unknown model {model_id}")
-    S, P = _lib.MODEL_S[model_id], _lib.MODEL_P[model_id]
+    S, P = _model_dims("sde_simulate", model_id)
     _require_gpu(theta, x_start)
     if theta.dtype != torch.float32 or x_start.dtype != torch.float32:
         raise _lib.VissmError("sde_simulate: fp32 theta and x_start expected")
@@ -945,13 +964,12 @@ def sde_simulate(model_id: int, theta: torch.Tensor, x_start: torch.Tensor, H: i
                               f"{tuple(theta.shape)} and {tuple(x_start.shape)}")
     with_obs = obs_std is not None
     if with_obs and model_id == _lib.MODEL_SV:
-        raise _lib.VissmError("sde_simulate: no observation model for SV (its first coordinate is the observed series)")
+        raise _sv_refused("sde_simulate", "observation model")
     B, H, t0 = theta.shape[0], int(H), int(t0)
     NS = 2 * S if with_obs else S
     if H < 0 or t0 < 0 or (t0 + H) * NS >= 2 ** 31:
         raise _lib.VissmError(f"sde_simulate: bad horizon H={H} t0={t0} ((t0 + H) * {NS} must stay below 2^31)")
-    if not 0 <= int(row0) < 2 ** 64:
-        raise _lib.VissmError(f"sde_simulate: row0={row0} outside [0, 2^64)")
+    key, row = _key_and_row("sde_simulate", seed, row0)
     dev = theta.device
     x = torch.empty(B, S, H, dtype=torch.float32, device=dev)
     y = torch.empty(B, S, H, dtype=torch.float32, device=dev) if with_obs else None
@@ -959,8 +977,7 @@ def sde_simulate(model_id: int, theta: torch.Tensor, x_start: torch.Tensor, H: i
         return x, y, x_start.clone()
     x_end = torch.empty(B, S, dtype=torch.float32, device=dev)
     d = _lib.SimDesc(model_id, B, H, t0, NS, float(dt), float(obs_std) if with_obs else 0.0, int(with_obs))
-    check(_lib.load().vissm_sde_simulate(ctypes.byref(d), ctypes.c_uint64(seed & (2 ** 64 - 1)),
-                                         ctypes.c_uint64(int(row0)), ptr(theta), ptr(x_start), ptr(x), ptr(y),
+    check(_lib.load().vissm_sde_simulate(ctypes.byref(d), key, row, ptr(theta), ptr(x_start), ptr(x), ptr(y),
                                          ptr(x_end), _lib.stream_handle(dev)), "vissm_sde_simulate")
     return x, y, x_end
 
@@ -1003,12 +1020,7 @@ def particle_filter(model_id: int, theta: torch.Tensor, x_start: torch.Tensor, o
         raise _lib.VissmError(f"particle_filter: proposal {proposal!r}, one of {PF_PROPOSALS} expected")
     if proposal == "adapted" and not 0.0 < float(obs_std) < float("inf"):
         raise _lib.VissmError(f"particle_filter: the adapted proposal needs a positive, finite obs_std, got {obs_std}")
-    if model_id not in _lib.MODEL_S:
-        raise _lib.VissmError(f"particle_filter: unknown model {model_id}")
-    if model_id == _lib.MODEL_SV:
-        raise _lib.VissmError("particle_filter: no observation model for SV (its first coordinate is the observed "
-                              "series)")
-    S, P = _lib.MODEL_S[model_id], _lib.MODEL_P[model_id]
+    S, P = _model_dims("particle_filter", model_id, sv_lacks="observation model")
     N = int(N)
     if N not in _lib.PF_PARTICLES:
         raise _lib.VissmError(f"particle_filter: N={N} particles, one of {_lib.PF_PARTICLES} expected")
@@ -1036,8 +1048,7 @@ def particle_filter(model_id: int, theta: torch.Tensor, x_start: torch.Tensor, o
     if H < 0 or t0 < 0 or t0 + H > T_total or (t0 + H) * S >= 2 ** 31:
         raise _lib.VissmError(f"particle_filter: bad horizon H={H} t0={t0} for {T_total} observations "
                               f"((t0 + H) * {S} must stay below 2^31)")
-    if not 0 <= int(row0) < 2 ** 64:
-        raise _lib.VissmError(f"particle_filter: row0={row0} outside [0, 2^64)")
+    key, row = _key_and_row("particle_filter", seed, row0)
     if loglik_in is not None:
         if not loglik_in.is_cuda or loglik_in.device != dev or loglik_in.dtype != torch.float64 or \
                 tuple(loglik_in.shape) != (K,) or not loglik_in.is_contiguous():
@@ -1053,8 +1064,7 @@ def particle_filter(model_id: int, theta: torch.Tensor, x_start: torch.Tensor, o
         return ParticleFilterResult(loglik, ll_inc, ess, state_end, cl, qt, at)
     d = _lib.PfDesc(model_id, K, N, H, t0, T_total, float(dt), float(obs_std))
     name = "vissm_particle_filter_adapted" if proposal == "adapted" else "vissm_particle_filter"
-    check(getattr(_lib.load(), name)(ctypes.byref(d), ctypes.c_uint64(seed & (2 ** 64 - 1)),
-                                     ctypes.c_uint64(int(row0)), ptr(theta), ptr(x_start), ptr(obs), ptr(obs_bin),
+    check(getattr(_lib.load(), name)(ctypes.byref(d), key, row, ptr(theta), ptr(x_start), ptr(obs), ptr(obs_bin),
                                      ptr(loglik_in), ptr(loglik), ptr(ll_inc), ptr(ess), ptr(state_end), ptr(cl),
                                      ptr(qt), ptr(at), _lib.stream_handle(dev)), name)
     return ParticleFilterResult(loglik, ll_inc, ess, state_end, cl, qt, at)
@@ -1080,12 +1090,7 @@ def particle_smooth(model_id: int, theta: torch.Tensor, cloud: torch.Tensor, dt:
     row0 + k N + j under `seed` at counter (t0 + t, 2, row).  x_next [K M, S] is the target of the last step (None:
     a uniform draw over the live particles there); a call over the steps before with x_next = this call's x_first
     and its own t0 continues bitwise.  AR, LV and FHN; SV has no filter and is refused."""
-    if model_id not in _lib.MODEL_S:
-        raise _lib.VissmError(f"particle_smooth: unknown model {model_id}")
-    if model_id == _lib.MODEL_SV:
-        raise _lib.VissmError("particle_smooth: no particle filter for SV (its first coordinate is the observed "
-                              "series)")
-    S, P = _lib.MODEL_S[model_id], _lib.MODEL_P[model_id]
+    S, P = _model_dims("particle_smooth", model_id, sv_lacks="particle filter")
     _require_gpu(theta, cloud)
     for name, t in (("theta", theta), ("cloud", cloud)):
         if t.dtype != torch.float32:
@@ -1106,8 +1111,7 @@ def particle_smooth(model_id: int, theta: torch.Tensor, cloud: torch.Tensor, dt:
         raise _lib.VissmError(f"particle_smooth: K={K} filters, at most 65535 per call")
     if H < 1 or t0 < 0 or t0 + H >= 2 ** 31:
         raise _lib.VissmError(f"particle_smooth: bad horizon H={H} t0={t0} (H >= 1 and t0 + H below 2^31)")
-    if not 0 <= int(row0) < 2 ** 64:
-        raise _lib.VissmError(f"particle_smooth: row0={row0} outside [0, 2^64)")
+    key, row = _key_and_row("particle_smooth", seed, row0)
     dev = theta.device
     if cloud.device != dev:
         raise _lib.VissmError("particle_smooth: all tensors on one device expected")
@@ -1121,8 +1125,7 @@ def particle_smooth(model_id: int, theta: torch.Tensor, cloud: torch.Tensor, dt:
     ix = torch.empty(K * M, H, dtype=torch.int32, device=dev) if idx else None
     qt = torch.empty(K, H, M, N, dtype=torch.int64, device=dev) if trace else None
     d = _lib.PsDesc(model_id, K, N, M, H, t0, float(dt))
-    check(_lib.load().vissm_particle_smooth(ctypes.byref(d), ctypes.c_uint64(seed & (2 ** 64 - 1)),
-                                            ctypes.c_uint64(int(row0)), ptr(theta), ptr(cloud), ptr(x_next),
+    check(_lib.load().vissm_particle_smooth(ctypes.byref(d), key, row, ptr(theta), ptr(cloud), ptr(x_next),
                                             ptr(paths), ptr(x_first), ptr(ix), ptr(qt), _lib.stream_handle(dev)),
           "vissm_particle_smooth")
     return ParticleSmoothResult(paths, x_first, ix, qt)

@@ -18,20 +18,8 @@ import torch
 
 from . import _lib
 from .nma import Engine, ModelDef, Batch, AdamaxSlots, ScalarLog
-from .summary import DEFAULT_PROBS, _check_probs, column_summary
-
-# Philox key of the forecast's normals: the engine's seed xor this (Engine.draw keys eps by the seed itself and the
-# q(theta) base draw by seed ^ 0x5DEECE66D)
-FORECAST_SEED_XOR = 0xF02ECA57
-# Philox key of the particle filter's normals and resampling integers: a fourth key next to the forecast's
-FILTER_SEED_XOR = 0xF117E2ED
-# Philox key of the particle smoother's selection words: a fifth key
-SMOOTH_SEED_XOR = 0x5300714E
-# device bytes of the filter's cloud [K N, S, T] fp32 that particle_smoother() may keep for its backward pass
-SMOOTH_CLOUD_BYTES = 8 << 30
-# device bytes one forecast launch may write per output ([B, S, chunk] fp32): the default chunk is the largest
-# multiple of the kernel's tile under it
-FORECAST_CHUNK_BYTES = 256 << 20
+from .diagnostics import (PosteriorDiagnostics, FORECAST_SEED_XOR, FILTER_SEED_XOR, SMOOTH_SEED_XOR,  # noqa: F401
+                          SMOOTH_CLOUD_BYTES, FORECAST_CHUNK_BYTES)   # (the constants: re-exported for callers)
 
 
 @dataclass
@@ -72,8 +60,8 @@ class DistCtx:
         return t
 
 
-class VISSMBase:
-    """Engine + optimisers + reference training loop."""
+class VISSMBase(PosteriorDiagnostics):
+    """Engine + optimisers + reference training loop (the posterior diagnostics: diagnostics.py)."""
 
     def __init__(self, mdef: ModelDef, table, theta_spec: ThetaSpec, p: int, pre_train: bool,
                  early_stopping: float, learn_rate: float, grad_clip: float, device=None, seed: int = 1,
@@ -576,298 +564,3 @@ class VISSMBase:
             os.makedirs(d, exist_ok=True)
         with open(PATH_obs, "w") as f:
             np.savetxt(f, np.reshape(paths, (paths.shape[0], -1)) if paths.shape[1] > 1 else paths[:, 0, :])
-
-    # ------------------------------------------------------------------ posterior summaries
-    @torch.no_grad()
-    def sample_paths_theta(self, starts: np.ndarray, step: int = 0):
-        """sample_paths with the draw's theta next to the paths: (x [B, D, M+1], theta [B, P])."""
-        batch = self.engine.make_batch(np.asarray(starts))
-        out = self.forward(batch, step)
-        return self.engine.lf_sample(out["z"], batch), out["theta"]
-
-    @torch.no_grad()
-    def posterior_summary(self, probs=DEFAULT_PROBS) -> Dict[str, np.ndarray]:
-        """Mean, sd and quantile bands of the latent path over time and of theta, over exactly the samples save_paths
-        would write (the same window starts, draws and step) and, with several ranks, over all of them -- computed on
-        the GPU (summary.column_summary), so only the summaries reach the host instead of every sample of every
-        window (AR.py:323-362 and the offline quantiles of vis.py).  paths/{mean, sd} are [D, T], paths/quantiles
-        [Q, D, T]; theta/{mean, sd} [P], theta/quantiles [Q, P] come from the first window's draw, log-parameters
-        exponentiated as in histograms().  Every rank takes part in the collectives and gets the same result."""
-        M = self.batch_dims
-        parts = []
-        res: Dict[str, np.ndarray] = {"probs": np.asarray(list(probs), dtype=np.float64)}
-        for idx in np.arange(0, self.target_len(), M):
-            x, theta = self.sample_paths_theta(np.tile(idx, self.p_local), step=self.global_step)
-            xs = x[:, :, 1:]
-            B, D, m = xs.shape
-            x2 = xs[:, 0, :] if D == 1 else xs.reshape(B, D * m)   # a pitched, offset view / a contiguous copy
-            parts.append((D, m, column_summary(x2.float(), probs, self.dist)))
-            if "theta/mean" not in res:
-                th = theta.detach().float()
-                pos = list(self.mdef.theta_pos)
-                if any(pos):
-                    th = torch.where(torch.tensor(pos, device=th.device), th.exp(), th)
-                for k, v in column_summary(th.contiguous(), probs, self.dist).items():
-                    res[f"theta/{k}"] = v
-        for k in ("mean", "sd", "n_valid"):
-            res[f"paths/{k}"] = np.concatenate([s[k].reshape(D, m) for D, m, s in parts], axis=1)
-        res["paths/quantiles"] = np.concatenate([s["quantiles"].reshape(-1, D, m) for D, m, s in parts], axis=2)
-        return res
-
-    def save_summary(self, PATH: str, probs=DEFAULT_PROBS) -> Dict[str, np.ndarray]:
-        """posterior_summary written as one .npz by rank 0 (every rank computes it: the collectives need them all)."""
-        res = self.posterior_summary(probs)
-        if self.dist.rank == 0:
-            d = os.path.dirname(PATH)
-            if d:
-                os.makedirs(d, exist_ok=True)
-            with open(PATH, "wb") as f:
-                np.savez(f, **res)
-        return res
-
-    # ------------------------------------------------------------------ posterior-predictive forecasts
-    def forecast_chunk(self) -> int:
-        """Steps per launch of forecast() by default: [p_local, S, chunk] fp32 stays under FORECAST_CHUNK_BYTES."""
-        steps = FORECAST_CHUNK_BYTES // (4 * _lib.MODEL_S[self.mdef.model_id] * max(self.p_local, 1))
-        return max(_lib.SIM_TILE, steps // _lib.SIM_TILE * _lib.SIM_TILE)
-
-    @torch.no_grad()
-    def forecast(self, horizon: int, probs=DEFAULT_PROBS, obs: bool = False, chunk: Optional[int] = None
-                 ) -> Dict[str, np.ndarray]:
-        """Posterior-predictive forecast: the SDE simulated `horizon` steps past the data on the GPU
-        (ops.sde_simulate), from every sample of the draw of the last window save_paths / posterior_summary visit
-        (same start, same step) -- its theta and its path's last state -- and summarised over the samples of all
-        ranks with summary.column_summary.  forecast/{mean, sd, n_valid} are [S, H], forecast/quantiles [Q, S, H]
-        (S the state's coordinates; 2 for SV, the observed series and its log-volatility); obs=True adds the same
-        four under forecast/obs/ for simulated observations x + obs_std * noise (not SV); forecast/start =
-        target_len(), the index of the first forecast step.  A trajectory that leaves the model's domain is NaN
-        from there on and n_valid counts the rest: the bands condition on survival.  The normals are
-        Philox rows global_step * p + rank * p_local + b under key seed ^ FORECAST_SEED_XOR, so the result does not
-        depend on the number of ranks; `chunk` steps per launch (default forecast_chunk()), chained through the end
-        state, change nothing either.  Every rank takes part in the collectives and gets the same result."""
-        from . import ops
-        H = int(horizon)
-        if H < 0:
-            raise ValueError(f"forecast horizon {horizon} < 0")
-        p = _check_probs(probs)
-        md = self.mdef
-        if obs and md.model_id == _lib.MODEL_SV:
-            raise ValueError("forecast(obs=True): SV has no observation model (its first coordinate is the observed "
-                             "series)")
-        chunk = self.forecast_chunk() if chunk is None else int(chunk)
-        if chunk < 1:
-            raise ValueError(f"forecast chunk {chunk} < 1")
-        last = int(np.arange(0, self.target_len(), self.batch_dims)[-1])
-        x, theta = self.sample_paths_theta(np.tile(last, self.p_local), step=self.global_step)
-        th = theta.detach().float().contiguous()
-        state = x[:, :, -1].float().contiguous()
-        seed = self.engine.seed ^ FORECAST_SEED_XOR
-        row0 = self.global_step * self.p + self.dist.rank * self.p_local
-        S, Q = _lib.MODEL_S[md.model_id], p.size   # the state's coordinates (SV: 2; its mdef.D counts the latent one)
-        groups = ("forecast", "forecast/obs") if obs else ("forecast",)
-        parts = {g: [] for g in groups}
-        for t0 in range(0, H, chunk):
-            m = min(chunk, H - t0)
-            xs, ys, state = ops.sde_simulate(md.model_id, th, state, m, md.dt, seed, row0, t0=t0,
-                                             obs_std=md.obs_std if obs else None)
-            for g, v in zip(groups, (xs, ys)):
-                parts[g].append((m, column_summary(v.view(v.shape[0], S * m), probs, self.dist)))
-        res: Dict[str, np.ndarray] = {"probs": p, "forecast/start": np.asarray(self.target_len(), dtype=np.int64)}
-        for g in groups:
-            for k, dt_ in (("mean", np.float64), ("sd", np.float64), ("n_valid", np.int64)):
-                res[f"{g}/{k}"] = np.concatenate([s[k].reshape(S, m) for m, s in parts[g]] +
-                                                 [np.zeros((S, 0), dtype=dt_)], axis=1)
-            res[f"{g}/quantiles"] = np.concatenate([s["quantiles"].reshape(Q, S, m) for m, s in parts[g]] +
-                                                   [np.zeros((Q, S, 0))], axis=2)
-        return res
-
-    def save_forecast(self, PATH: str, horizon: int, probs=DEFAULT_PROBS, obs: bool = False,
-                      chunk: Optional[int] = None) -> Dict[str, np.ndarray]:
-        """forecast written as one .npz by rank 0 (every rank computes it: the collectives need them all)."""
-        res = self.forecast(horizon, probs, obs, chunk)
-        if self.dist.rank == 0:
-            d = os.path.dirname(PATH)
-            if d:
-                os.makedirs(d, exist_ok=True)
-            with open(PATH, "wb") as f:
-                np.savez(f, **res)
-        return res
-
-    # ------------------------------------------------------------------ particle filter
-    def filter_chunk(self, n_theta: int, n_particles: int) -> int:
-        """Steps per launch of particle_filter() by default: the [K N, S, chunk] fp32 cloud stays under
-        FORECAST_CHUNK_BYTES (a multiple of the forecast tile, at least one)."""
-        steps = FORECAST_CHUNK_BYTES // (4 * _lib.MODEL_S[self.mdef.model_id] * max(n_theta * n_particles, 1))
-        return max(_lib.SIM_TILE, steps // _lib.SIM_TILE * _lib.SIM_TILE)
-
-    @torch.no_grad()
-    def particle_filter(self, n_theta: int = 64, n_particles: int = 1024, probs=DEFAULT_PROBS,
-                        chunk: Optional[int] = None, proposal: str = "bootstrap") -> Dict[str, np.ndarray]:
-        """A check of the fitted posterior that does not come out of the flows: K = n_theta bootstrap particle filters
-        of N = n_particles particles each (ops.particle_filter), one per theta sample, over the model's observations
-        from its x0.  theta = global samples 0 .. K - 1 of the first window's draw posterior_summary uses (same
-        start, same step): rank 0's first rows, broadcast, so K <= p_local.  Every rank runs the identical
-        deterministic launches and holds the same result; nothing is sharded.
-
-        filter/loglik [K] float64 estimates log p(y | theta_k) (-inf: every particle died); filter/theta [K, P] the
-        raw theta rows; filter/ll_inc and filter/ess [K, T] the per-step increments (0 where nothing is observed) and
-        effective sample sizes (N there); filter/{mean, sd, n_valid} [S, T] and filter/quantiles [Q, S, T] summarise
-        the K N equally weighted post-resampling particles of each step (summary.column_summary): the theta_k are iid
-        from q(theta), so this is the filtering distribution averaged over q(theta).  T = min(target_len(), the
-        observations' length).  Philox key seed ^ FILTER_SEED_XOR, rows global_step K N + k N + i; `chunk` steps per
-        launch (default filter_chunk()), chained through the end state and the running log-likelihood, change
-        nothing.  SV has no observation model: ValueError.
-
-        proposal = "adapted" runs the fully adapted filter (ops.particle_filter(proposal="adapted")) on the same
-        theta rows, key, rows and chunks: a much lower variance of filter/loglik where obs_std is small against the
-        process noise.  The result then also carries filter/proposal = "adapted", and its bands summarise the
-        post-propagation particles (n_valid leaves out the LV particles that left the orthant after a resampling).
-        With the default every launch and every entry is the bootstrap filter's, with no new key.  Any other value:
-        VissmError."""
-        return self._filter_pass(n_theta, n_particles, probs, chunk, None, proposal)[0]
-
-    def _filter_pass(self, n_theta, n_particles, probs, chunk, keep, proposal="bootstrap"):
-        """particle_filter()'s launches and result; with keep = (M, cap) the arguments of particle_smoother() are
-        checked before the first launch and every chunk's cloud stays on the device: (res, theta, [(t0, cloud)])."""
-        from . import ops
-        md = self.mdef
-        what = "particle_filter" if keep is None else "particle_smoother"
-        if proposal not in ops.PF_PROPOSALS:
-            raise _lib.VissmError(f"{what}: proposal {proposal!r}, one of {ops.PF_PROPOSALS} expected")
-        if md.model_id == _lib.MODEL_SV or getattr(self, "filter_data", None) is None:
-            raise ValueError(f"{what}: SV has no observation model (its first coordinate is the observed "
-                             "series)")
-        K, N = int(n_theta), int(n_particles)
-        if N not in _lib.PF_PARTICLES:
-            raise ValueError(f"particle_filter: n_particles={N}, one of {_lib.PF_PARTICLES} expected")
-        if not 1 <= K <= self.p_local:
-            raise ValueError(f"particle_filter: n_theta={K} outside 1 .. p_local = {self.p_local}")
-        p = _check_probs(probs)
-        chunk = self.filter_chunk(K, N) if chunk is None else int(chunk)
-        if chunk < 1:
-            raise ValueError(f"particle_filter chunk {chunk} < 1")
-        dev = self.engine.device
-        S, Q = _lib.MODEL_S[md.model_id], p.size
-        obs_h, bin_h, x0_h = self.filter_data
-        T = min(int(self.target_len()), obs_h.shape[1])
-        if keep is not None:
-            M, cap = keep
-            if not (_lib.PS_MIN_PATHS <= M <= N and M & (M - 1) == 0):
-                raise ValueError(f"particle_smoother: n_paths={M}, a power of two in {_lib.PS_MIN_PATHS} .. "
-                                 f"n_particles = {N} expected")
-            if T < 1:
-                raise ValueError("particle_smoother: no step to smooth")
-            if 4 * K * N * S * T > cap:
-                raise ValueError(f"particle_smoother: the filter's cloud [{K} * {N}, {S}, {T}] fp32 takes "
-                                 f"{4 * K * N * S * T} bytes, more than SMOOTH_CLOUD_BYTES = {cap}: lower n_theta or "
-                                 "n_particles")
-        obs = torch.as_tensor(np.ascontiguousarray(obs_h[:, :T]), device=dev)
-        obs_bin = torch.as_tensor(np.ascontiguousarray(bin_h[:, :T]), device=dev)
-        x0 = torch.as_tensor(x0_h, device=dev)
-        _, theta = self.sample_paths_theta(np.tile(0, self.p_local), step=self.global_step)
-        th = theta.detach().float()[:K].contiguous()
-        if self.dist.world > 1:
-            import torch.distributed as dist
-            dist.broadcast(th, src=dist.get_global_rank(self.dist.group, 0) if self.dist.group is not None else 0,
-                           group=self.dist.group)
-        seed = self.engine.seed ^ FILTER_SEED_XOR
-        row0 = self.global_step * K * N
-        state, ll = x0, None
-        incs, esss, parts, clouds = [], [], [], []
-        for t0 in range(0, T, chunk):
-            m = min(chunk, T - t0)
-            r = ops.particle_filter(md.model_id, th, state, obs, obs_bin, md.dt, md.obs_std, N, seed, row0, t0=t0,
-                                    loglik_in=ll, cloud=True, H=m, proposal=proposal)
-            state, ll = r.state_end, r.loglik
-            incs.append(r.ll_inc)
-            esss.append(r.ess)
-            parts.append((m, column_summary(r.cloud.view(K * N, S * m), probs, None)))
-            if keep is not None:
-                clouds.append((t0, r.cloud))
-        res: Dict[str, np.ndarray] = {"probs": p, "filter/theta": th.cpu().numpy()}
-        if proposal != "bootstrap":
-            res["filter/proposal"] = np.asarray(proposal)
-        res["filter/loglik"] = ll.cpu().numpy() if ll is not None else np.zeros(K)
-        res["filter/ll_inc"] = torch.cat(incs + [torch.zeros(K, 0, device=dev)], 1).cpu().numpy()
-        res["filter/ess"] = torch.cat(esss + [torch.zeros(K, 0, device=dev)], 1).cpu().numpy()
-        for k, dt_ in (("mean", np.float64), ("sd", np.float64), ("n_valid", np.int64)):
-            res[f"filter/{k}"] = np.concatenate([s[k].reshape(S, m) for m, s in parts] +
-                                                [np.zeros((S, 0), dtype=dt_)], axis=1)
-        res["filter/quantiles"] = np.concatenate([s["quantiles"].reshape(Q, S, m) for m, s in parts] +
-                                                 [np.zeros((Q, S, 0))], axis=2)
-        return res, th, clouds
-
-    def save_filter(self, PATH: str, n_theta: int = 64, n_particles: int = 1024, probs=DEFAULT_PROBS,
-                    chunk: Optional[int] = None, proposal: str = "bootstrap") -> Dict[str, np.ndarray]:
-        """particle_filter written as one .npz by rank 0 (every rank computes the same result)."""
-        res = self.particle_filter(n_theta, n_particles, probs, chunk, proposal)
-        if self.dist.rank == 0:
-            d = os.path.dirname(PATH)
-            if d:
-                os.makedirs(d, exist_ok=True)
-            with open(PATH, "wb") as f:
-                np.savez(f, **res)
-        return res
-
-    # ------------------------------------------------------------------ particle smoother
-    @torch.no_grad()
-    def particle_smoother(self, n_theta: int = 64, n_particles: int = 1024, n_paths: int = 64, probs=DEFAULT_PROBS,
-                          chunk: Optional[int] = None, proposal: str = "bootstrap") -> Dict[str, np.ndarray]:
-        """The check that is comparable with what the engine fits: the variational posterior over the latent path is
-        a smoothing distribution p(x_t | y_1:T), the filter's bands are filtering distributions p(x_t | y_1:t).
-        Forward filtering, then backward simulation (ops.particle_smooth): the forward pass is particle_filter()'s,
-        launch for launch (same theta rows, key, rows and chunks), with every chunk's cloud kept on the device --
-        4 K N S T bytes, refused with ValueError before any launch above SMOOTH_CLOUD_BYTES; then M = n_paths
-        trajectories per filter (a power of two, 64 <= M <= N) are drawn backward through the chunks, last to first,
-        each chunk's first state the target of the one before, under the key seed ^ SMOOTH_SEED_XOR and rows
-        global_step K N + k N + j.
-
-        Returns every filter/* entry of particle_filter() plus smooth/{mean, sd, n_valid} [S, T] and
-        smooth/quantiles [Q, S, T], the column summary of the K M trajectories of each step: the smoothing
-        distribution averaged over q(theta), to lay over paths/quantiles of posterior_summary().  A filter that died
-        contributes NaN trajectories, which n_valid leaves out.  `chunk` changes nothing; every rank runs the same
-        launches and holds the same result.  SV has no observation model: ValueError.
-
-        proposal = "adapted": the forward pass is particle_filter(proposal="adapted")'s, whose cloud is, like the
-        bootstrap's, an equally weighted sample of each filtering law; the backward pass is untouched."""
-        from . import ops
-        md = self.mdef
-        K, N, M = int(n_theta), int(n_particles), int(n_paths)
-        res, th, clouds = self._filter_pass(K, N, probs, chunk, (M, SMOOTH_CLOUD_BYTES), proposal)
-        S, Q = _lib.MODEL_S[md.model_id], res["probs"].size
-        seed = self.engine.seed ^ SMOOTH_SEED_XOR
-        row0 = self.global_step * K * N
-        parts, x_next = [], None
-        while clouds:
-            t0, cloud = clouds.pop()          # last chunk first; the cloud is freed once it is smoothed
-            r = ops.particle_smooth(md.model_id, th, cloud, md.dt, M, seed, row0, t0=t0, x_next=x_next)
-            x_next = r.x_first
-            m = cloud.shape[2]
-            parts.append((m, column_summary(r.paths.view(K * M, S * m), probs, None)))
-            del cloud, r
-        parts.reverse()
-        for k in ("mean", "sd", "n_valid"):
-            res[f"smooth/{k}"] = np.concatenate([s[k].reshape(S, m) for m, s in parts], axis=1)
-        res["smooth/quantiles"] = np.concatenate([s["quantiles"].reshape(Q, S, m) for m, s in parts], axis=2)
-        return res
-
-    def save_smoother(self, PATH: str, n_theta: int = 64, n_particles: int = 1024, n_paths: int = 64,
-                      probs=DEFAULT_PROBS, chunk: Optional[int] = None,
-                      proposal: str = "bootstrap") -> Dict[str, np.ndarray]:
-        """particle_smoother written as one .npz by rank 0 (every rank computes the same result)."""
-        res = self.particle_smoother(n_theta, n_particles, n_paths, probs, chunk, proposal)
-        if self.dist.rank == 0:
-            d = os.path.dirname(PATH)
-            if d:
-                os.makedirs(d, exist_ok=True)
-            with open(PATH, "wb") as f:
-                np.savez(f, **res)
-        return res
-
-    def _keep_filter_data(self, obs, obs_bin, x0):
-        """The raw constructor arguments the particle filter reads (the feature tables are built from copies):
-        obs, obs_bin as [S, T] fp32, x0 as [S] fp32."""
-        S = _lib.MODEL_S[self.mdef.model_id]
-        self.filter_data = (np.asarray(obs, dtype=np.float32).reshape(S, -1),
-                            np.asarray(obs_bin, dtype=np.float32).reshape(S, -1),
-                            np.asarray(x0, dtype=np.float32).reshape(S))
