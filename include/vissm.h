@@ -738,6 +738,59 @@ int vissm_particle_smooth(const VissmPsDesc* d, uint64_t seed, uint64_t row0,
                           uint64_t* q_trace /* [K][H][M][N] or NULL: tests only */, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Particle filter and smoother of the stochastic-volatility model.  The entries above refuse SV because it has no
+ * obs_std / obs_bin observation model; it can be filtered all the same: the observed series y is the first coordinate
+ * of the Euler-Maruyama state, the latent log-volatility h the second, and the two noises are independent
+ * (csrc/svf_math.hpp; the reference's SV_dense.py:203-223):
+ *   y_t | y_t-1, h_t-1  ~  N(y_t-1 (1 + dt th0),  dt y_t-1^2 e^{h_t-1})
+ *   h_t | h_t-1         ~  N(h_t-1 + dt (th1 - e^th2 h_t-1),  dt e^{2 th3})
+ * The weight of a step depends on the particle's state before the move and the move does not depend on y_t, so
+ * "weight on the pre-step state, resample, move" is the exactly fully adapted filter.
+ *
+ * vissm_sv_filter takes a VissmPfDesc with model = VISSM_MODEL_SV (anything else is refused); obs_std is ignored and
+ * there is no obs_bin: every step is observed.  obs is the series y[0 .. T_total], T_total + 1 values; x_start
+ * [K N] holds h at absolute step t0 (h_0 for t0 = 0), theta [K][4].  Geometry, N, Philox streams (AR's: n_stream = 1,
+ * counter (ta / 4, 0, row); resampling on counter word 1 of row0 + k N), the integer pipeline, ll_inc, ess, loglik_in /
+ * loglik, state_end, the traces, a NULL cloud, the death of a filter at W = 0 and chaining are vissm_particle_filter's.
+ * Step ta = t0 + t:
+ *   logw_i = -1/2 log 2 pi - log(sqrt(dt) |y[ta]|) - h_i / 2 - 1/2 r^2 / (dt y[ta]^2 e^{h_i}),
+ *            r = y[ta + 1] - y[ta] - dt th0 y[ta];  -inf for a dead particle (h not finite)
+ *   m, q_i, W, ll_inc, ess, U, tau_j, anc[j] from these as in vissm_particle_filter
+ *   slot j takes h of particle anc[j] and moves it with the normal of its own row: the second coordinate of
+ *   vissm_sde_simulate's SV step, bit for bit.
+ * cloud [K N][1][H]: column t holds h after the move, an equally weighted sample of p(h_ta+1 | y_0:ta+1, theta).
+ * loglik estimates log p(y_1:T | y_0, h_0, theta).  A y[ta] of 0 makes every weight NaN and kills the filter.
+ * Refused by host arithmetic: a null descriptor or pointer, N not one of the five, negative shapes, t0 + H > T_total,
+ * t0 + H >= 2^31, K N >= 2^31, dt not positive and finite.  Bitwise reproducible; filter k's bits depend on (seed,
+ * row0 + k N, theta_k, N, y) only.  vissm_sv_filter_lds_bytes: the LDS one block declares (0 = bad N).
+ *
+ * vissm_sv_smooth is vissm_particle_smooth over that cloud (VissmPsDesc with model = VISSM_MODEL_SV; the same
+ * geometry, M, selection on counter word 2, terminal rule, NaN propagation, x_first / x_next chaining, idx and
+ * q_trace).  Column c (absolute ca = t0 + c) holds h_ca+1, and y_ca+2 depends on it, so the backward weight is not
+ * the transition alone: for a trajectory whose next state is xt
+ *   logw_i = log f(xt | h_i) + logw of h_i for (y[ca + 1], y[ca + 2]), less a constant of theta and dt.
+ * It therefore takes obs and T_total as well, and refuses t0 + H + (x_next ? 1 : 0) > T_total: every column with a
+ * next state reads y[ca + 2].  vissm_sv_smooth_lds_bytes: the LDS one block declares (0 = bad N or M).
+ * ------------------------------------------------------------------------- */
+int32_t vissm_sv_filter_lds_bytes(int32_t N);
+int vissm_sv_filter(const VissmPfDesc* d, uint64_t seed, uint64_t row0,
+                    const float* theta /* [K][4] */, const float* x_start /* [K N] */,
+                    const float* obs /* [T_total + 1] */,
+                    const double* loglik_in /* [K] or NULL */, double* loglik /* [K] */,
+                    float* ll_inc /* [K][H] */, float* ess /* [K][H] */, float* state_end /* [K N] */,
+                    float* cloud /* [K N][1][H] or NULL */, uint64_t* q_trace /* [K][H][N] or NULL */,
+                    int32_t* anc_trace /* [K][H][N] or NULL */, void* stream);
+
+int32_t vissm_sv_smooth_lds_bytes(int32_t N, int32_t M);
+int vissm_sv_smooth(const VissmPsDesc* d, uint64_t seed, uint64_t row0,
+                    const float* theta /* [K][4] */, const float* cloud /* [K N][1][H], vissm_sv_filter's */,
+                    const float* obs /* [T_total + 1] */, int32_t T_total,
+                    const float* x_next /* [K M] or NULL: the target of column H - 1 */,
+                    float* paths /* [K M][1][H] */, float* x_first /* [K M] */,
+                    int32_t* idx /* [K M][H] or NULL */, uint64_t* q_trace /* [K][H][M][N] or NULL: tests only */,
+                    void* stream);
+
+/* ---------------------------------------------------------------------------
  * Opt-in kernel timing (for bench.py's live roofline): when enabled, the flow
  * entry points bracket their main kernel with hipEvents on the launch stream.
  * kind: VISSM_PROF_FLOW_FWD / VISSM_PROF_FLOW_BWD (flow kernels),

@@ -215,6 +215,11 @@ SIGNATURES = {
     "vissm_particle_filter_adapted": (_i32, [ctypes.POINTER(PfDesc), _u64, _u64] + [_c_void_p] * 12 + [_c_void_p]),
     "vissm_particle_smooth_lds_bytes": (_i32, [_i32, _i32, _i32]),
     "vissm_particle_smooth": (_i32, [ctypes.POINTER(PsDesc), _u64, _u64] + [_c_void_p] * 7 + [_c_void_p]),
+    "vissm_sv_filter_lds_bytes": (_i32, [_i32]),
+    "vissm_sv_filter": (_i32, [ctypes.POINTER(PfDesc), _u64, _u64] + [_c_void_p] * 11 + [_c_void_p]),
+    "vissm_sv_smooth_lds_bytes": (_i32, [_i32, _i32]),
+    "vissm_sv_smooth": (_i32, [ctypes.POINTER(PsDesc), _u64, _u64] + [_c_void_p] * 3 + [_i32] + [_c_void_p] * 5 +
+                        [_c_void_p]),
     "vissm_profile_enable": (None, [_i32]),
     "vissm_profile_read": (_i32, [_i32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_i64)]),
     "vissm_profile_reset": (None, []),

@@ -4,7 +4,8 @@
 // of rng_math.hpp (Philox4x32-10 and u01) against tests/philox_ref.py,
 // of pf_math.hpp (the particle filter's integer weights and resampling) against Python big-int arithmetic,
 // of ps_math.hpp (the particle smoother's backward weights and integer selection) against float64 and big ints,
-// and of gp_math.hpp (the adapted filter's predictive weight and conditional draw) against numpy.linalg in float64.
+// of gp_math.hpp (the adapted filter's predictive weight and conditional draw) against numpy.linalg in float64,
+// and of svf_math.hpp (the stochastic-volatility filter's weight and move, the smoother's pair weight) against float64.
 // Not part of the product path: libvissm_hostcheck.so is loaded only by tests/.
 #include <cstddef>
 
@@ -16,6 +17,7 @@
 #include "pf_math.hpp"
 #include "ps_math.hpp"
 #include "gp_math.hpp"
+#include "svf_math.hpp"
 
 extern "C" {
 
@@ -230,6 +232,33 @@ uint64_t hc_gp_filter_step(int model, const float* x, int n, const float* th, fl
     default:
       return gp_filter_step_t<VISSM_MODEL_FHN>(x, n, th, dt, y, bin, obs_std, normals, U, x_out, q, anc, C, m_out);
   }
+}
+
+// The stochastic-volatility filter's and smoother's shared math (svf_math.hpp: the code sv_filter_kernel and
+// sv_smooth_kernel run), theta raw [4].  hc_svf_logw: the weight of the pre-step state h for (y_prev, y_now);
+// hc_svf_move: the next h from one normal, with the death rule; hc_svf_pair_logw: the backward weight of particle h for
+// target xt with the next two observations, *dropped the constant it leaves out; hc_svf_filter_step and hc_svf_draw:
+// one whole filter step and one whole backward draw run serially (svf::filter_step, svf::draw).
+float hc_svf_logw(float h, float y_prev, float y_now, const float* th, float dt) {
+  return vissm::svf::state_logw(h, y_prev, y_now, vissm::sim::prepare<VISSM_MODEL_SV>(th, dt));
+}
+float hc_svf_move(float h, const float* th, float dt, float n) {
+  return vissm::svf::move(h, vissm::sim::prepare<VISSM_MODEL_SV>(th, dt), n);
+}
+float hc_svf_pair_logw(float h, float xt, float y_next, float y_next2, const float* th, float dt, float* dropped) {
+  using namespace vissm::svf;
+  const SPar s = sprepare(th, dt);
+  *dropped = dropped_const(th, dt);
+  return pair_logw(particle(h, obs_prep(y_next, y_next2, s.p), s), s, xt);
+}
+uint64_t hc_svf_filter_step(const float* h, int n, const float* th, float dt, float y_prev, float y_now,
+                            const float* normals, uint32_t U, float* h_out, uint64_t* q, int32_t* anc, uint64_t* C,
+                            float* m_out) {
+  return vissm::svf::filter_step(h, n, th, dt, y_prev, y_now, normals, U, h_out, q, anc, C, m_out);
+}
+int hc_svf_draw(const float* h, int n, const float* th, float dt, int have_next, float xt, float y_next, float y_next2,
+                uint32_t U, uint64_t* q, float* m) {
+  return vissm::svf::draw(h, n, th, dt, have_next, xt, y_next, y_next2, U, q, m);
 }
 
 // the C ABI's struct layouts as the C compiler sees them (the ctypes mirrors in viforssms_amd/_lib.py are

@@ -15,6 +15,8 @@
 // the adapted filter's predictive weight, conditional mean and Cholesky factor (gp_math.hpp) against a double
 // restatement of the general 2 x 2 formulas over every mask and obs_std from 0.05 to 1000 transition sd, the clamp,
 // and whole serial filter steps with dead particles;
+// the stochastic-volatility filter's weight and move and the smoother's pair weight (svf_math.hpp) against a double
+// restatement, sim_math.hpp's own SV step and sv_trans' joint density, with whole serial steps and draws;
 // any sanitizer report aborts the run (-fno-sanitize-recover=all).
 // Exit 0 = all checks passed.  Not part of the product path.
 #include <cmath>
@@ -60,6 +62,14 @@ float hc_gp_l11(float p11, float l10);
 uint64_t hc_gp_filter_step(int model, const float* x, int n, const float* th, float dt, const float* y,
                            const float* bin, float obs_std, const float* normals, uint32_t U, float* x_out,
                            uint64_t* q, int32_t* anc, uint64_t* C, float* m_out);
+float hc_svf_logw(float h, float y_prev, float y_now, const float* th, float dt);
+float hc_svf_move(float h, const float* th, float dt, float n);
+float hc_svf_pair_logw(float h, float xt, float y_next, float y_next2, const float* th, float dt, float* dropped);
+uint64_t hc_svf_filter_step(const float* h, int n, const float* th, float dt, float y_prev, float y_now,
+                            const float* normals, uint32_t U, float* h_out, uint64_t* q, int32_t* anc, uint64_t* C,
+                            float* m_out);
+int hc_svf_draw(const float* h, int n, const float* th, float dt, int have_next, float xt, float y_next, float y_next2,
+                uint32_t U, uint64_t* q, float* m);
 }
 
 namespace {
@@ -675,6 +685,106 @@ int check_gp() {
   return bad;
 }
 
+// svf_math.hpp: the weight against a double restatement; the move against hc_sim_step's second coordinate, bit for
+// bit; pair_logw plus the dropped constant against sv_trans' lp of the joint step (y_next, h) -> (y_next2, xt), which
+// factorises into the transition of h and the weight; whole serial filter steps and backward draws with dead
+// particles, a NaN target, the terminal rule, no live particle and y_prev = 0.
+int check_svf() {
+  int bad = 0;
+  for (float dt : {1.f, 0.1f})
+    for (int rep = 0; rep < 400; ++rep) {
+      float th[5] = {0.001f, -0.6f, -2.5257287f, -0.6931472f, 0.f};
+      for (int i = 0; i < 4; ++i) th[i] += static_cast<float>(uniform(-0.2, 0.2));
+      const float h = static_cast<float>(uniform(-12.0, -3.0));
+      const float y0 = static_cast<float>(uniform(1.0, 15.0) * (uniform(0.0, 1.0) < 0.5 ? -1.0 : 1.0));
+      const double sd = std::sqrt(static_cast<double>(dt)) * std::fabs(y0) * std::exp(0.5 * h);
+      const float y1 = static_cast<float>(y0 + sd * uniform(-3.0, 3.0));
+      const float n = static_cast<float>(uniform(-3.0, 3.0));
+      const double r = static_cast<double>(y1) - y0 - static_cast<double>(dt) * th[0] * y0;
+      const double want = -0.5 * std::log(2.0 * M_PI) - std::log(std::sqrt(static_cast<double>(dt)) * std::fabs(y0)) -
+                          0.5 * h - 0.5 * r * r / (dt * static_cast<double>(y0) * y0 * std::exp(static_cast<double>(h)));
+      const float lw = hc_svf_logw(h, y0, y1, th, dt);
+      // (r cancels two nearby floats: the bar is the relative rounding of y1 - y0 carried into r^2 / var)
+      const double rel = 4e-7 * (std::fabs(y1) + std::fabs(y0)) / std::fmax(std::fabs(r), 1e-30);
+      if (!std::isfinite(lw) || std::fabs(lw - want) > 2e-5 * std::fmax(1.0, std::fabs(want)) +
+                                                           rel * r * r / (sd * sd)) {
+        std::printf("svf: logw %.9g vs %.9g\n", lw, want);
+        ++bad;
+      }
+      const float x[2] = {y0, h}, nn[2] = {static_cast<float>(uniform(-2.0, 2.0)), n};
+      float out[2];
+      hc_sim_step(2, x, th, dt, nn, out);
+      const float mv = hc_svf_move(h, th, dt, n);
+      if (to_bits(mv) != to_bits(out[1])) { std::printf("svf: move %.9g vs em_step %.9g\n", mv, out[1]); ++bad; }
+      const float xt = out[1];
+      const float xh[2] = {y0, h}, xn[2] = {y1, xt};
+      float dropped = 0.f;
+      const float pw = hc_svf_pair_logw(h, xt, y0, y1, th, dt, &dropped);
+      const float lp = lp_of(2, xh, xn, th, dt);
+      if (!std::isfinite(pw) || std::fabs((pw + dropped) - lp) > 4e-5f * std::fmax(1.f, std::fabs(lp)) +
+                                                                     static_cast<float>(rel * r * r / (sd * sd))) {
+        std::printf("svf: pair_logw %.9g + %.9g vs lp %.9g\n", pw, dropped, lp);
+        ++bad;
+      }
+    }
+  const float th[5] = {0.001f, -0.6f, -2.5257287f, -0.6931472f, 0.f};
+  if (hc_svf_logw(NAN, 1.f, 1.1f, th, 1.f) != -INFINITY || hc_svf_logw(INFINITY, 1.f, 1.1f, th, 1.f) != -INFINITY ||
+      !std::isnan(hc_svf_move(NAN, th, 1.f, 0.f)) || !std::isnan(hc_svf_move(-INFINITY, th, 1.f, 0.f))) {
+    std::printf("svf: dead particle\n");
+    ++bad;
+  }
+  for (int n : {64, 1024}) {
+    std::vector<float> h(n), nn(n), ho(n);
+    for (int i = 0; i < n; ++i) {
+      h[i] = i % 4 == 1 ? NAN : static_cast<float>(uniform(-10.0, -6.0));
+      nn[i] = static_cast<float>(uniform(-2.0, 2.0));
+    }
+    std::vector<uint64_t> q(n), C(n);
+    std::vector<int32_t> anc(n);
+    float m = 0.f;
+    uint64_t W = hc_svf_filter_step(h.data(), n, th, 1.f, 5.25f, 5.31f, nn.data(), 0x654321u, ho.data(), q.data(),
+                                    anc.data(), C.data(), &m);
+    uint64_t top = 0;
+    for (int i = 0; i < n; ++i) {
+      top = std::max(top, q[i]);
+      if (i % 4 == 1 && q[i] != 0) { std::printf("svf: a dead particle has weight\n"); ++bad; }
+      if (anc[i] < 0 || anc[i] >= n || q[anc[i]] == 0 || to_bits(ho[i]) != to_bits(hc_svf_move(h[anc[i]], th, 1.f, nn[i]))) {
+        std::printf("svf: slot %d ancestor %d\n", i, anc[i]);
+        ++bad;
+      }
+    }
+    if (W == 0 || top != (1ull << 40) || !std::isfinite(m)) { std::printf("svf: filter step\n"); ++bad; }
+    if (hc_svf_filter_step(h.data(), n, th, 1.f, 0.f, 5.31f, nn.data(), 1u, ho.data(), q.data(), anc.data(), C.data(),
+                           &m) != 0 || !std::isnan(ho[0])) {
+      std::printf("svf: y_prev = 0\n");
+      ++bad;
+    }
+    for (uint32_t U : {0u, 0x12345678u, 0xFFFFFFFFu}) {
+      int idx = hc_svf_draw(h.data(), n, th, 1.f, 1, -8.3f, 5.25f, 5.31f, U, q.data(), &m);
+      top = 0;
+      for (int i = 0; i < n; ++i) {
+        top = std::max(top, q[i]);
+        if (i % 4 == 1 && q[i] != 0) { std::printf("svf: a dead particle is drawn\n"); ++bad; }
+      }
+      if (idx < 0 || idx >= n || idx % 4 == 1 || q[idx] == 0 || top != (1ull << 40)) { std::printf("svf: draw\n"); ++bad; }
+      idx = hc_svf_draw(h.data(), n, th, 1.f, 0, 0.f, 0.f, 0.f, U, q.data(), &m);
+      for (int i = 0; i < n; ++i)
+        if (q[i] != (i % 4 == 1 ? 0ull : 1ull << 40)) { std::printf("svf: terminal weight %d\n", i); ++bad; }
+      if (idx < 0 || idx % 4 == 1 || m != 0.f) { std::printf("svf: terminal draw\n"); ++bad; }
+      if (hc_svf_draw(h.data(), n, th, 1.f, 1, NAN, 5.25f, 5.31f, U, q.data(), &m) != -1) { std::printf("svf: NaN target\n"); ++bad; }
+    }
+    std::fill(h.begin(), h.end(), NAN);
+    if (hc_svf_filter_step(h.data(), n, th, 1.f, 5.25f, 5.31f, nn.data(), 1u, ho.data(), q.data(), anc.data(), C.data(),
+                           &m) != 0 || !std::isnan(ho[n - 1]) ||
+        hc_svf_draw(h.data(), n, th, 1.f, 1, -8.f, 5.25f, 5.31f, 9u, q.data(), &m) != -1 ||
+        hc_svf_draw(h.data(), n, th, 1.f, 0, 0.f, 0.f, 0.f, 9u, q.data(), &m) != -1) {
+      std::printf("svf: no live particle\n");
+      ++bad;
+    }
+  }
+  return bad;
+}
+
 }  // namespace
 
 int main() {
@@ -700,6 +810,7 @@ int main() {
   bad += check_pf();
   bad += check_ps();
   bad += check_gp();
+  bad += check_svf();
   bad += check_colkey();
   bad += check_select();
   for (int which = 0; which < 8; ++which) {

@@ -305,6 +305,128 @@ class PosteriorDiagnostics:
         """particle_smoother written as one .npz by rank 0 (every rank computes the same result)."""
         return self._save_npz(PATH, self.particle_smoother(n_theta, n_particles, n_paths, probs, chunk, proposal))
 
+    # ------------------------------------------------------------------ stochastic volatility: filter and smoother
+    @torch.no_grad()
+    def volatility_filter(self, n_theta: int = 64, n_particles: int = 1024, probs=DEFAULT_PROBS,
+                          chunk: Optional[int] = None) -> Dict[str, np.ndarray]:
+        """particle_filter() for the SV family, which that method refuses: SV has no obs_std / obs_bin observation
+        model, but its observed series y is the first coordinate of the state and the latent log-volatility h the
+        second, so h can be filtered on p(y_t+1 | y_t, h_t) (ops.sv_filter).  The weight depends on the pre-step
+        state and the move does not depend on y, so this is the exactly fully adapted filter, at no extra cost.
+
+        K = n_theta filters of N = n_particles particles, one per theta sample, from h_0 = the model's x0 over y =
+        the model's obs; theta rows, key (seed ^ FILTER_SEED_XOR), rows (global_step K N + k N + i), chunks and
+        chaining as particle_filter().  The result has particle_filter()'s keys with S = 1 and T = target_len(), and
+        filter/proposal = "adapted": filter/loglik [K] estimates log p(y_1:T | y_0, h_0, theta_k); column t of
+        filter/{mean, sd, n_valid, quantiles} summarises the K N equally weighted particles of p(h_t+1 | y_0:t+1).
+        ValueError before any launch: a family other than SV, a y[0 .. T] that is not finite, a y[0 .. T - 1] equal
+        to 0 (the density degenerates)."""
+        return self._volatility_pass(n_theta, n_particles, probs, chunk, None)[0]
+
+    def _volatility_pass(self, n_theta, n_particles, probs, chunk, keep):
+        """volatility_filter()'s launches and result; with keep = (M, cap) the arguments of volatility_smoother() are
+        checked before the first launch and every chunk's cloud stays on the device: (res, theta, obs, [(t0, cloud)])."""
+        from . import ops
+        md = self.mdef
+        what = "volatility_filter" if keep is None else "volatility_smoother"
+        if md.model_id != _lib.MODEL_SV:
+            raise ValueError(f"{what}: the {md.family} family has an observation model: particle_filter() and "
+                             "particle_smoother() are its checks; this one is SV's")
+        K, N = int(n_theta), int(n_particles)
+        if N not in _lib.PF_PARTICLES:
+            raise ValueError(f"{what}: n_particles={N}, one of {_lib.PF_PARTICLES} expected")
+        if not 1 <= K <= self.p_local:
+            raise ValueError(f"{what}: n_theta={K} outside 1 .. p_local = {self.p_local}")
+        p = _check_probs(probs)
+        chunk = self.filter_chunk(K, N) if chunk is None else int(chunk)
+        if chunk < 1:
+            raise ValueError(f"{what} chunk {chunk} < 1")
+        y_h = np.asarray(self.obs, dtype=np.float32).reshape(-1)
+        T = min(int(self.target_len()), y_h.shape[0] - 1)
+        y_h = np.ascontiguousarray(y_h[:T + 1])
+        if not np.isfinite(y_h).all():
+            raise ValueError(f"{what}: the observed series y[0 .. {T}] is not finite")
+        if np.any(y_h[:T] == 0.0):
+            raise ValueError(f"{what}: y[{int(np.flatnonzero(y_h[:T] == 0.0)[0])}] = 0: the density of the next "
+                             "observation degenerates there")
+        if keep is not None:
+            M, cap = keep
+            if not (_lib.PS_MIN_PATHS <= M <= N and M & (M - 1) == 0):
+                raise ValueError(f"{what}: n_paths={M}, a power of two in {_lib.PS_MIN_PATHS} .. n_particles = {N} "
+                                 "expected")
+            if T < 1:
+                raise ValueError(f"{what}: no step to smooth")
+            if 4 * K * N * T > cap:
+                raise ValueError(f"{what}: the filter's cloud [{K} * {N}, 1, {T}] fp32 takes {4 * K * N * T} bytes, "
+                                 f"more than SMOOTH_CLOUD_BYTES = {cap}: lower n_theta or n_particles")
+        dev = self.engine.device
+        Q = p.size
+        obs = torch.as_tensor(y_h, device=dev)
+        _, theta = self.sample_paths_theta(np.tile(0, self.p_local), step=self.global_step)
+        th = theta.detach().float()[:K].contiguous()
+        if self.dist.world > 1:
+            import torch.distributed as dist
+            dist.broadcast(th, src=dist.get_global_rank(self.dist.group, 0) if self.dist.group is not None else 0,
+                           group=self.dist.group)
+        seed = self.engine.seed ^ FILTER_SEED_XOR
+        row0 = self.global_step * K * N
+        state, ll = torch.full((1,), float(self.x0), dtype=torch.float32, device=dev), None
+        incs, esss, parts, clouds = [], [], [], []
+        for t0 in range(0, T, chunk):
+            m = min(chunk, T - t0)
+            r = ops.sv_filter(th, state, obs, md.dt, N, seed, row0, t0=t0, loglik_in=ll, cloud=True, H=m)
+            state, ll = r.state_end, r.loglik
+            incs.append(r.ll_inc)
+            esss.append(r.ess)
+            parts.append((m, column_summary(r.cloud.view(K * N, m), probs, None)))
+            if keep is not None:
+                clouds.append((t0, r.cloud))
+        res: Dict[str, np.ndarray] = {"probs": p, "filter/theta": th.cpu().numpy(),
+                                      "filter/proposal": np.asarray("adapted")}
+        res["filter/loglik"] = ll.cpu().numpy() if ll is not None else np.zeros(K)
+        res["filter/ll_inc"] = torch.cat(incs + [torch.zeros(K, 0, device=dev)], 1).cpu().numpy()
+        res["filter/ess"] = torch.cat(esss + [torch.zeros(K, 0, device=dev)], 1).cpu().numpy()
+        res.update(stack_bands("filter", parts, 1, Q))
+        return res, th, obs, clouds
+
+    def save_volatility_filter(self, PATH: str, n_theta: int = 64, n_particles: int = 1024, probs=DEFAULT_PROBS,
+                               chunk: Optional[int] = None) -> Dict[str, np.ndarray]:
+        """volatility_filter written as one .npz by rank 0 (every rank computes the same result)."""
+        return self._save_npz(PATH, self.volatility_filter(n_theta, n_particles, probs, chunk))
+
+    @torch.no_grad()
+    def volatility_smoother(self, n_theta: int = 64, n_particles: int = 1024, n_paths: int = 64, probs=DEFAULT_PROBS,
+                            chunk: Optional[int] = None) -> Dict[str, np.ndarray]:
+        """particle_smoother() for the SV family: volatility_filter()'s forward pass, launch for launch, with every
+        chunk's cloud kept on the device (4 K N T bytes, refused above SMOOTH_CLOUD_BYTES), then M = n_paths
+        trajectories of h per filter drawn backward through the chunks (ops.sv_smooth) under the key seed ^
+        SMOOTH_SEED_XOR and rows global_step K N + k N + j.  Returns every filter/* entry plus smooth/{mean, sd,
+        n_valid} [1, T] and smooth/quantiles [Q, 1, T]: column t is p(h_t+1 | y_0:T) averaged over q(theta), to lay
+        directly over paths/quantiles of posterior_summary().  `chunk` changes nothing; every rank runs the same
+        launches and holds the same result.  Refusals as volatility_filter()."""
+        from . import ops
+        md = self.mdef
+        K, N, M = int(n_theta), int(n_particles), int(n_paths)
+        res, th, obs, clouds = self._volatility_pass(K, N, probs, chunk, (M, SMOOTH_CLOUD_BYTES))
+        Q = res["probs"].size
+        seed = self.engine.seed ^ SMOOTH_SEED_XOR
+        row0 = self.global_step * K * N
+        parts, x_next = [], None
+        while clouds:
+            t0, cloud = clouds.pop()          # last chunk first; the cloud is freed once it is smoothed
+            r = ops.sv_smooth(th, cloud, obs, md.dt, M, seed, row0, t0=t0, x_next=x_next)
+            x_next = r.x_first
+            m = cloud.shape[2]
+            parts.append((m, column_summary(r.paths.view(K * M, m), probs, None)))
+            del cloud, r
+        res.update(stack_bands("smooth", parts[::-1], 1, Q))
+        return res
+
+    def save_volatility_smoother(self, PATH: str, n_theta: int = 64, n_particles: int = 1024, n_paths: int = 64,
+                                 probs=DEFAULT_PROBS, chunk: Optional[int] = None) -> Dict[str, np.ndarray]:
+        """volatility_smoother written as one .npz by rank 0 (every rank computes the same result)."""
+        return self._save_npz(PATH, self.volatility_smoother(n_theta, n_particles, n_paths, probs, chunk))
+
     def _keep_filter_data(self, obs, obs_bin, x0):
         """The raw constructor arguments the particle filter reads (the feature tables are built from copies):
         obs, obs_bin as [S, T] fp32, x0 as [S] fp32."""

@@ -1129,3 +1129,124 @@ def particle_smooth(model_id: int, theta: torch.Tensor, cloud: torch.Tensor, dt:
                                             ptr(paths), ptr(x_first), ptr(ix), ptr(qt), _lib.stream_handle(dev)),
           "vissm_particle_smooth")
     return ParticleSmoothResult(paths, x_first, ix, qt)
+
+
+# ---------------------------------------------------------------------------------------
+# stochastic volatility: particle filter and smoother of the latent log-volatility
+# ---------------------------------------------------------------------------------------
+def _sv_series(fn: str, obs: torch.Tensor, dev) -> int:
+    """T_total of the series y[0 .. T_total] (a contiguous fp32 GPU vector of T_total + 1 values)."""
+    _require_gpu(obs)
+    if obs.dtype != torch.float32 or obs.dim() != 1 or obs.shape[0] < 1 or obs.device != dev:
+        raise _lib.VissmError(f"{fn}: obs: an fp32 vector y[0 .. T] on theta's device expected, got "
+                              f"{obs.dtype} {tuple(obs.shape)}")
+    return obs.shape[0] - 1
+
+
+def sv_filter(theta: torch.Tensor, x_start: torch.Tensor, obs: torch.Tensor, dt: float, N: int, seed: int, row0: int,
+              t0: int = 0, loglik_in: Optional[torch.Tensor] = None, cloud: bool = True, H: Optional[int] = None,
+              trace: bool = False) -> ParticleFilterResult:
+    """K particle filters of the stochastic-volatility model's latent log-volatility h, N particles each, one per row
+    of theta [K, 4] (raw), over steps t0 .. t0 + H - 1 of the observed series obs = y[0 .. T] (T + 1 values; H = T - t0
+    by default); vissm_sv_filter.  Step ta weights each particle's h *before* the move on p(y[ta + 1] | y[ta], h),
+    resamples in integers and moves the survivors with the prior transition, which is the exact conditional: the
+    fully adapted filter.  x_start: h at step t0, [K N], [K N, 1] or one value for every particle.  Cloud column t is
+    an equally weighted sample of p(h_{t0+t+1} | y_{0 : t0+t+1}); shapes, traces and chaining as particle_filter
+    with S = 1.  Particle (k, i) uses Philox row row0 + k N + i with AR's stream (n_stream = 1)."""
+    N = int(N)
+    if N not in _lib.PF_PARTICLES:
+        raise _lib.VissmError(f"sv_filter: N={N} particles, one of {_lib.PF_PARTICLES} expected")
+    if not 0.0 < float(dt) < float("inf"):
+        raise _lib.VissmError(f"sv_filter: dt must be positive and finite, got {dt}")
+    _require_gpu(theta, x_start)
+    P = _lib.MODEL_P[_lib.MODEL_SV]
+    for name, t in (("theta", theta), ("x_start", x_start)):
+        if t.dtype != torch.float32:
+            raise _lib.VissmError(f"sv_filter: fp32 {name} expected, got {t.dtype}")
+    if theta.dim() != 2 or theta.shape[1] != P:
+        raise _lib.VissmError(f"sv_filter: theta [K, {P}] expected, got {tuple(theta.shape)}")
+    K, dev = theta.shape[0], theta.device
+    if K * N >= 2 ** 31:
+        raise _lib.VissmError(f"sv_filter: K N = {K} * {N} reaches 2^31")
+    if x_start.numel() == 1:
+        x_start = x_start.reshape(1).expand(K * N).contiguous()
+    if x_start.numel() != K * N or x_start.dim() > 2 or x_start.device != dev:
+        raise _lib.VissmError(f"sv_filter: x_start [{K * N}] (or one value) on theta's device expected, got "
+                              f"{tuple(x_start.shape)}")
+    T_total, t0 = _sv_series("sv_filter", obs, dev), int(t0)
+    H = T_total - t0 if H is None else int(H)
+    if H < 0 or t0 < 0 or t0 + H > T_total or t0 + H >= 2 ** 31:
+        raise _lib.VissmError(f"sv_filter: bad horizon H={H} t0={t0} for a series of {T_total} transitions")
+    key, row = _key_and_row("sv_filter", seed, row0)
+    if loglik_in is not None:
+        if not loglik_in.is_cuda or loglik_in.device != dev or loglik_in.dtype != torch.float64 or \
+                tuple(loglik_in.shape) != (K,) or not loglik_in.is_contiguous():
+            raise _lib.VissmError(f"sv_filter: loglik_in: a contiguous float64 GPU tensor [{K}] expected")
+    loglik = torch.empty(K, dtype=torch.float64, device=dev)
+    ll_inc = torch.empty(K, H, dtype=torch.float32, device=dev)
+    ess = torch.empty(K, H, dtype=torch.float32, device=dev)
+    state_end = torch.empty(K * N, 1, dtype=torch.float32, device=dev)
+    cl = torch.empty(K * N, 1, H, dtype=torch.float32, device=dev) if cloud else None
+    qt = torch.empty(K, H, N, dtype=torch.int64, device=dev) if trace else None
+    at = torch.empty(K, H, N, dtype=torch.int32, device=dev) if trace else None
+    if K == 0:
+        return ParticleFilterResult(loglik, ll_inc, ess, state_end, cl, qt, at)
+    d = _lib.PfDesc(_lib.MODEL_SV, K, N, H, t0, T_total, float(dt), 0.0)
+    check(_lib.load().vissm_sv_filter(ctypes.byref(d), key, row, ptr(theta), ptr(x_start), ptr(obs), ptr(loglik_in),
+                                      ptr(loglik), ptr(ll_inc), ptr(ess), ptr(state_end), ptr(cl), ptr(qt), ptr(at),
+                                      _lib.stream_handle(dev)), "vissm_sv_filter")
+    return ParticleFilterResult(loglik, ll_inc, ess, state_end, cl, qt, at)
+
+
+def sv_smooth(theta: torch.Tensor, cloud: torch.Tensor, obs: torch.Tensor, dt: float, M: int, seed: int, row0: int,
+              t0: int = 0, x_next: Optional[torch.Tensor] = None, idx: bool = False,
+              trace: bool = False) -> ParticleSmoothResult:
+    """M backward-simulation trajectories of h per filter over cloud [K N, 1, H], the columns t0 .. t0 + H - 1 that
+    sv_filter wrote for theta [K, 4] and the series obs = y[0 .. T]; vissm_sv_smooth.  Column c holds h_{t0+c+1}, and
+    y[t0 + c + 2] depends on it, so the backward weight of particle i for the next state xt is the transition density
+    times p(y[t0 + c + 2] | y[t0 + c + 1], h_i).  Selection words, x_next [K M, 1] / x_first chaining, the terminal
+    rule (x_next None: a uniform draw over the live particles of the last column), idx and trace as particle_smooth.
+    Every column with a next state needs y[t0 + c + 2]: t0 + H (+ 1 with x_next) <= T."""
+    P = _lib.MODEL_P[_lib.MODEL_SV]
+    _require_gpu(theta, cloud)
+    for name, t in (("theta", theta), ("cloud", cloud)):
+        if t.dtype != torch.float32:
+            raise _lib.VissmError(f"sv_smooth: fp32 {name} expected, got {t.dtype}")
+    if theta.dim() != 2 or theta.shape[1] != P or theta.shape[0] < 1:
+        raise _lib.VissmError(f"sv_smooth: theta [K >= 1, {P}] expected, got {tuple(theta.shape)}")
+    if not 0.0 < float(dt) < float("inf"):
+        raise _lib.VissmError(f"sv_smooth: dt must be positive and finite, got {dt}")
+    K, M = theta.shape[0], int(M)
+    if cloud.dim() != 3 or cloud.shape[1] != 1 or cloud.shape[0] % K:
+        raise _lib.VissmError(f"sv_smooth: a contiguous cloud [{K} N, 1, H] expected, got {tuple(cloud.shape)}")
+    N, H, t0 = cloud.shape[0] // K, cloud.shape[2], int(t0)
+    if N not in _lib.PF_PARTICLES:
+        raise _lib.VissmError(f"sv_smooth: N={N} particles, one of {_lib.PF_PARTICLES} expected")
+    if not (_lib.PS_MIN_PATHS <= M <= N and M & (M - 1) == 0):
+        raise _lib.VissmError(f"sv_smooth: M={M} trajectories, a power of two in {_lib.PS_MIN_PATHS} .. N = {N} "
+                              "expected")
+    if K > 65535:
+        raise _lib.VissmError(f"sv_smooth: K={K} filters, at most 65535 per call")
+    dev = theta.device
+    if cloud.device != dev:
+        raise _lib.VissmError("sv_smooth: all tensors on one device expected")
+    T_total = _sv_series("sv_smooth", obs, dev)
+    need = t0 + H + (1 if x_next is not None else 0)
+    if H < 1 or t0 < 0 or t0 + H >= 2 ** 31 or need > T_total:
+        raise _lib.VissmError(f"sv_smooth: bad horizon H={H} t0={t0}: every column with a next state reads "
+                              f"y[t0 + c + 2], up to y[{need}] of y[0 .. {T_total}]")
+    key, row = _key_and_row("sv_smooth", seed, row0)
+    theta = theta.contiguous()
+    if x_next is not None:
+        if not x_next.is_cuda or x_next.device != dev or x_next.dtype != torch.float32 or \
+                tuple(x_next.shape) != (K * M, 1) or not x_next.is_contiguous():
+            raise _lib.VissmError(f"sv_smooth: x_next: a contiguous fp32 GPU tensor [{K * M}, 1] expected")
+    paths = torch.empty(K * M, 1, H, dtype=torch.float32, device=dev)
+    x_first = torch.empty(K * M, 1, dtype=torch.float32, device=dev)
+    ix = torch.empty(K * M, H, dtype=torch.int32, device=dev) if idx else None
+    qt = torch.empty(K, H, M, N, dtype=torch.int64, device=dev) if trace else None
+    d = _lib.PsDesc(_lib.MODEL_SV, K, N, M, H, t0, float(dt))
+    check(_lib.load().vissm_sv_smooth(ctypes.byref(d), key, row, ptr(theta), ptr(cloud), ptr(obs), T_total,
+                                      ptr(x_next), ptr(paths), ptr(x_first), ptr(ix), ptr(qt),
+                                      _lib.stream_handle(dev)), "vissm_sv_smooth")
+    return ParticleSmoothResult(paths, x_first, ix, qt)

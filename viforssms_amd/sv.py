@@ -33,6 +33,7 @@ class VI_SSM(VISSMBase):
                          int(no_flows), int(kernel_len), int(batch_dims), int(feat_window))
         self.target_dims = int(target_dims)
         self.obs = np.asarray(obs)
+        self.x0 = float(x0)      # h_0: where volatility_filter() starts its particles
         super().__init__(mdef, table, theta_dist, p, pre_train, 1e99, learn_rate, grad_clip, device=device,
                          seed=seed, precision=precision, dist=dist, log_every=log_every, init_seed=init_seed)
 
@@ -66,7 +67,22 @@ def run(argv=None):
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--no-pretrain", action="store_true")
     ap.add_argument("--save-paths", default=None)
+    ap.add_argument("--filter", nargs=3, metavar=("K", "N", "PATH"), default=None,
+                    help="After training, run K particle filters of the log-volatility with N particles each (64 .. "
+                         "1024, a power of two) on the GPU and write the log-evidence estimates and filtering bands "
+                         "to this .npz file")
+    ap.add_argument("--smooth", nargs=4, metavar=("K", "N", "M", "PATH"), default=None,
+                    help="After training, run the K filters of --filter, draw M smoothing trajectories per filter by "
+                         "backward simulation (M a power of two, 64 <= M <= N) and write the filter's entries and "
+                         "the smoothing bands to this .npz file")
     args = ap.parse_args(argv)
+    for name, n_int in (("filter", 2), ("smooth", 3)):
+        v = getattr(args, name)
+        if v is not None:
+            try:
+                setattr(args, name, tuple(int(a) for a in v[:n_int]) + (v[n_int],))
+            except ValueError:
+                ap.error(f"--{name}: integers expected, got {v[:n_int]!r}")
     np.random.seed(1)
     ctx = init_distributed()
     obs = load_sv()
@@ -82,4 +98,9 @@ def run(argv=None):
         model.save_paths(args.save_paths)
     model.train(tensorboard_path="locally_variant/train/", save_path="model_saves/SV_model_%i_v211.ckpt" % args.batch_dims,
                 max_runs=args.steps)
+    if args.filter:
+        # every rank the same launches; rank 0 writes
+        model.save_volatility_filter(args.filter[2], args.filter[0], args.filter[1])
+    if args.smooth:
+        model.save_volatility_smoother(args.smooth[3], args.smooth[0], args.smooth[1], args.smooth[2])
     return model
