@@ -791,6 +791,47 @@ int vissm_sv_smooth(const VissmPsDesc* d, uint64_t seed, uint64_t row0,
                     void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Particle marginal Metropolis-Hastings over theta (Andrieu, Doucet & Holenstein 2010): C random-walk chains whose
+ * acceptance ratio holds vissm_particle_filter_adapted's unbiased estimate of p(y | theta), so each chain targets
+ * p(theta | y) exactly for any N.  AR, LV and FHN; one block per chain, N particles (the filter's five sizes), the
+ * chain's n_iter iterations inside one launch.  Chain c runs the absolute iterations i = it0 .. it0 + n_iter - 1; with
+ * r = row0 + (i C + c) N (csrc/mh_math.hpp):
+ *   words   philox4x32_10(ctr = (g, 2, lo32(r), hi32(r)), key = seed): g = 0, 1 -> Box-Muller (the base noise's) ->
+ *           xi_0 .. xi_7, the first P used; g = 2 -> first word x, u = ((x >> 8) + 1/2) 2^-24.  The normals of the
+ *           filter carry 0 in the second counter word and its resampling integers 1: the streams never meet.
+ *   theta'_p = float(theta_p + sum_{j <= p} L_pj xi_j), summed in double in ascending j; prop_chol = L [P][P] fp32, lower
+ *   lp(theta) = -1/2 sum_p ((theta_p - m_p) / s_p)^2 in double; prior [P][2] fp32 = (mean, sd) per parameter
+ *   ll' = the loglik vissm_particle_filter_adapted gives for K = C, row0' = row0 + i C N, t0 = 0, H = T_total, theta_c =
+ *           theta', every particle started at x_start [S]: the same rows, normals, weights and resampling integers
+ *   accept iff log(u) < (ll' - ll) + (lp' - lp), in double, in this arrangement: a dead proposal (ll' = -inf) is
+ *           rejected, a chain at ll = -inf accepts any finite proposal, and -inf against -inf (NaN) is rejected.
+ * ll_cur [C] is required: the estimate that goes with theta_cur (vissm_particle_filter_adapted with cloud = NULL).
+ *
+ * theta_chain [C][n_iter][P], ll_chain [C][n_iter] and accept [C][n_iter] hold the state after each decision;
+ * theta_end [C][P] and ll_end [C] the last one: a call with it0' = it0 + n_iter, theta_cur = theta_end and ll_cur =
+ * ll_end continues bitwise.  Optional traces for tests, NULL in production: theta_prop [C][n_iter][P], ll_prop and logu
+ * [C][n_iter].  No atomics, no workspace; two launches are bitwise equal, and chain c's bits depend on the block index
+ * through r only.  Refused by host arithmetic (VISSM_EINVAL): SV, an unknown model, N not one of the five, C < 1,
+ * n_iter < 0, it0 < 0, it0 + n_iter >= 2^31, T_total S >= 2^31, obs_std <= 0 or not finite, a null pointer.
+ * vissm_pmmh_lds_bytes: the LDS one block declares, 8 N + 4 S N + 192 (host arithmetic; 0 = bad model or N).
+ * ------------------------------------------------------------------------- */
+typedef struct {
+  int32_t model, C, N, n_iter, it0, T_total;
+  float dt, obs_std;
+} VissmPmmhDesc;
+
+int32_t vissm_pmmh_lds_bytes(int32_t model, int32_t N);
+int vissm_pmmh(const VissmPmmhDesc* d, uint64_t seed, uint64_t row0,
+               const float* theta_cur /* [C][P] */, const double* ll_cur /* [C] */,
+               const float* prop_chol /* [P][P] lower */, const float* prior /* [P][2] (mean, sd) */,
+               const float* x_start /* [S] */, const float* obs /* [S][T_total] */,
+               const float* obs_bin /* [S][T_total] */,
+               float* theta_chain /* [C][n_iter][P] */, double* ll_chain /* [C][n_iter] */,
+               int32_t* accept /* [C][n_iter] */, float* theta_end /* [C][P] */, double* ll_end /* [C] */,
+               float* theta_prop /* [C][n_iter][P] or NULL */, double* ll_prop /* [C][n_iter] or NULL */,
+               double* logu /* [C][n_iter] or NULL */, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Opt-in kernel timing (for bench.py's live roofline): when enabled, the flow
  * entry points bracket their main kernel with hipEvents on the launch stream.
  * kind: VISSM_PROF_FLOW_FWD / VISSM_PROF_FLOW_BWD (flow kernels),

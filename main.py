@@ -59,6 +59,9 @@ def run(argv=None):
     if args.smooth:
         model.save_smoother(args.smooth[3], args.smooth[0], args.smooth[1], args.smooth[2],
                             proposal=args.filter_proposal)   # as the filter
+    if args.mcmc:
+        # every rank the same launches; rank 0 writes.  A quarter of the iterations is burn-in, as the default's
+        model.save_theta_mcmc(args.mcmc[3], args.mcmc[0], args.mcmc[1], args.mcmc[2], burn_in=args.mcmc[2] // 4)
     return model
 
 

@@ -130,6 +130,11 @@ class PsDesc(ctypes.Structure):
     _fields_ = [(n, _i32) for n in ("model", "K", "N", "M", "H", "t0")] + [("dt", _f32)]
 
 
+class PmmhDesc(ctypes.Structure):
+    _fields_ = ([(n, _i32) for n in ("model", "C", "N", "n_iter", "it0", "T_total")] +
+                [("dt", _f32), ("obs_std", _f32)])
+
+
 # exported symbol -> (restype, argtypes); tests check that every symbol of include/vissm.h is here
 SIGNATURES = {
     "vissm_last_error": (ctypes.c_char_p, []),
@@ -218,6 +223,8 @@ SIGNATURES = {
     "vissm_sv_filter_lds_bytes": (_i32, [_i32]),
     "vissm_sv_filter": (_i32, [ctypes.POINTER(PfDesc), _u64, _u64] + [_c_void_p] * 11 + [_c_void_p]),
     "vissm_sv_smooth_lds_bytes": (_i32, [_i32, _i32]),
+    "vissm_pmmh_lds_bytes": (_i32, [_i32, _i32]),
+    "vissm_pmmh": (_i32, [ctypes.POINTER(PmmhDesc), _u64, _u64] + [_c_void_p] * 15 + [_c_void_p]),
     "vissm_sv_smooth": (_i32, [ctypes.POINTER(PsDesc), _u64, _u64] + [_c_void_p] * 3 + [_i32] + [_c_void_p] * 5 +
                         [_c_void_p]),
     "vissm_profile_enable": (None, [_i32]),

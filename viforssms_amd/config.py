@@ -148,7 +148,19 @@ def handle_opts(argv=None):
                              "propagates blindly and weights on the observation; adapted weights on the predictive "
                              "p(y_t | x_t-1) and propagates from p(x_t | x_t-1, y_t), a much lower variance of the "
                              "log-evidence where obs_std is small against the process noise")
+    parser.add_argument("--mcmc", nargs=4, metavar=("C", "N", "ITER", "PATH"), default=None,
+                        help="After training, run C particle marginal Metropolis-Hastings chains of ITER iterations on "
+                             "the GPU, each with a fully adapted particle filter of N particles (64 .. 1024, a power of "
+                             "two), started at posterior theta samples, and write the draws of p(theta | y) after the "
+                             "default burn-in, their quantiles beside q(theta)'s and the split-R-hat to this .npz file")
     args = parser.parse_args(argv)
+    if args.mcmc is not None:
+        try:
+            args.mcmc = (int(args.mcmc[0]), int(args.mcmc[1]), int(args.mcmc[2]), args.mcmc[3])
+        except ValueError:
+            parser.error(f"--mcmc: C, N and ITER must be integers, got {args.mcmc[:3]!r}")
+        if args.mcmc[0] < 1 or args.mcmc[1] not in (64, 128, 256, 512, 1024) or args.mcmc[2] < 2:
+            parser.error("--mcmc: C >= 1, N one of 64, 128, 256, 512, 1024 and ITER >= 2 expected")
     if args.filter_proposal is not None and args.filter is None and args.smooth is None:
         parser.error("--filter-proposal applies to --filter and --smooth: give one of them")
     if args.filter_proposal is None:

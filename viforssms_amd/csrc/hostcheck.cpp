@@ -5,7 +5,8 @@
 // of pf_math.hpp (the particle filter's integer weights and resampling) against Python big-int arithmetic,
 // of ps_math.hpp (the particle smoother's backward weights and integer selection) against float64 and big ints,
 // of gp_math.hpp (the adapted filter's predictive weight and conditional draw) against numpy.linalg in float64,
-// and of svf_math.hpp (the stochastic-volatility filter's weight and move, the smoother's pair weight) against float64.
+// of svf_math.hpp (the stochastic-volatility filter's weight and move, the smoother's pair weight) against float64,
+// and of mh_math.hpp (the Metropolis-Hastings chain's words, proposal, log-prior and acceptance rule) against numpy.
 // Not part of the product path: libvissm_hostcheck.so is loaded only by tests/.
 #include <cstddef>
 
@@ -18,6 +19,7 @@
 #include "ps_math.hpp"
 #include "gp_math.hpp"
 #include "svf_math.hpp"
+#include "mh_math.hpp"
 
 extern "C" {
 
@@ -261,8 +263,33 @@ int hc_svf_draw(const float* h, int n, const float* th, float dt, int have_next,
   return vissm::svf::draw(h, n, th, dt, have_next, xt, y_next, y_next2, U, q, m);
 }
 
+// The Metropolis-Hastings chain's shared math (mh_math.hpp: the code pmmh_kernel runs).  hc_mh_row: the first Philox
+// row of iteration i of chain c; hc_mh_words: the block of group g; hc_mh_uniform / hc_mh_log_uniform: the decision's u
+// and log u from a word; hc_mh_xi: the eight normals of row r from box_muller4_ref (the kernel's come from the hardware
+// transcendentals); hc_mh_propose: theta' [P]; hc_mh_log_prior; hc_mh_accept: the decision.
+uint64_t hc_mh_row(uint64_t row0, uint64_t i, uint64_t C, uint64_t c, uint64_t N) {
+  return vissm::mh::row_of(row0, i, C, c, N);
+}
+void hc_mh_words(uint32_t g, uint64_t r, uint64_t seed, uint32_t out[4]) {
+  const vissm::u4 w = vissm::mh::words(g, r, seed);
+  out[0] = w.x; out[1] = w.y; out[2] = w.z; out[3] = w.w;
+}
+double hc_mh_uniform(uint32_t x) { return vissm::mh::uniform(x); }
+double hc_mh_log_uniform(uint32_t x) { return vissm::mh::log_uniform(x); }
+void hc_mh_xi(uint64_t r, uint64_t seed, float out[8]) {
+  vissm::mh::box_muller4_ref(vissm::mh::words(0u, r, seed), out);
+  vissm::mh::box_muller4_ref(vissm::mh::words(1u, r, seed), out + 4);
+}
+void hc_mh_propose(const float* th, const float* L, const float* xi, int P, float* out) {
+  vissm::mh::propose(th, L, xi, P, out);
+}
+double hc_mh_log_prior(const float* th, const float* prior, int P) { return vissm::mh::log_prior(th, prior, P); }
+int hc_mh_accept(double logu, double ll_prop, double ll_cur, double lp_prop, double lp_cur) {
+  return vissm::mh::accept(logu, ll_prop, ll_cur, lp_prop, lp_cur) ? 1 : 0;
+}
+
 // the C ABI's struct layouts as the C compiler sees them (the ctypes mirrors in viforssms_amd/_lib.py are
-// checked against these): which = 0 VissmFlowDesc, 1 VissmFlowParams, 2 VissmFlowGrads, 3 VissmElboData, 4 VissmColStatDesc, 5 VissmSimDesc, 6 VissmPfDesc, 7 VissmPsDesc; out = {size,
+// checked against these): which = 0 VissmFlowDesc, 1 VissmFlowParams, 2 VissmFlowGrads, 3 VissmElboData, 4 VissmColStatDesc, 5 VissmSimDesc, 6 VissmPfDesc, 7 VissmPsDesc, 8 VissmPmmhDesc; out = {size,
 // offset of the last field}
 void vissm_host_abi_layout(int which, size_t* out) {
   switch (which) {
@@ -273,6 +300,7 @@ void vissm_host_abi_layout(int which, size_t* out) {
     case 4: out[0] = sizeof(VissmColStatDesc); out[1] = offsetof(VissmColStatDesc, n_ranks); break;
     case 6: out[0] = sizeof(VissmPfDesc); out[1] = offsetof(VissmPfDesc, obs_std); break;
     case 7: out[0] = sizeof(VissmPsDesc); out[1] = offsetof(VissmPsDesc, dt); break;
+    case 8: out[0] = sizeof(VissmPmmhDesc); out[1] = offsetof(VissmPmmhDesc, obs_std); break;
     default: out[0] = sizeof(VissmElboData); out[1] = offsetof(VissmElboData, obs_stride); break;
   }
 }

@@ -17,6 +17,8 @@
 // and whole serial filter steps with dead particles;
 // the stochastic-volatility filter's weight and move and the smoother's pair weight (svf_math.hpp) against a double
 // restatement, sim_math.hpp's own SV step and sv_trans' joint density, with whole serial steps and draws;
+// the Metropolis-Hastings chain's words, uniform, proposal, log-prior and acceptance rule (mh_math.hpp) on their edge
+// cases: the counter's second word, u inside (0, 1), a zero factor, the -inf and NaN decisions;
 // any sanitizer report aborts the run (-fno-sanitize-recover=all).
 // Exit 0 = all checks passed.  Not part of the product path.
 #include <cmath>
@@ -70,6 +72,14 @@ uint64_t hc_svf_filter_step(const float* h, int n, const float* th, float dt, fl
                             float* m_out);
 int hc_svf_draw(const float* h, int n, const float* th, float dt, int have_next, float xt, float y_next, float y_next2,
                 uint32_t U, uint64_t* q, float* m);
+uint64_t hc_mh_row(uint64_t row0, uint64_t i, uint64_t C, uint64_t c, uint64_t N);
+void hc_mh_words(uint32_t g, uint64_t r, uint64_t seed, uint32_t out[4]);
+double hc_mh_uniform(uint32_t x);
+double hc_mh_log_uniform(uint32_t x);
+void hc_mh_xi(uint64_t r, uint64_t seed, float out[8]);
+void hc_mh_propose(const float* th, const float* L, const float* xi, int P, float* out);
+double hc_mh_log_prior(const float* th, const float* prior, int P);
+int hc_mh_accept(double logu, double ll_prop, double ll_cur, double lp_prop, double lp_cur);
 }
 
 namespace {
@@ -785,6 +795,60 @@ int check_svf() {
   return bad;
 }
 
+// mh_math.hpp: the words are Philox on counter (g, 2, lo(r), hi(r)); u stays inside (0, 1); a zero factor proposes
+// theta itself and L = I adds the normals; the log-prior of the mean is 0; the decision's -inf and NaN cases
+int check_mh() {
+  int bad = 0;
+  const uint64_t seed = 0x0123456789ABCDEFull, r = hc_mh_row(0xFFFFFFF0ull, 3, 5, 2, 64);
+  if (r != 0xFFFFFFF0ull + (3 * 5 + 2) * 64) { std::printf("mh: row\n"); ++bad; }
+  for (uint32_t g = 0; g < 3; ++g) {
+    const uint32_t ctr[4] = {g, 2u, static_cast<uint32_t>(r), static_cast<uint32_t>(r >> 32)};
+    const uint32_t key[2] = {static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32)};
+    uint32_t got[4], want[4];
+    hc_mh_words(g, r, seed, got);
+    hc_philox(ctr, key, want);
+    if (std::memcmp(got, want, sizeof got) != 0) { std::printf("mh: words of group %u\n", g); ++bad; }
+  }
+  for (uint32_t w : {0x00000000u, 0x000000FFu, 0x00000100u, 0xFFFFFF00u, 0xFFFFFFFFu}) {
+    const double u = hc_mh_uniform(w), lu = hc_mh_log_uniform(w);
+    if (!(u > 0.0 && u < 1.0) || u != (static_cast<double>(w >> 8) + 0.5) / 16777216.0 || !(lu < 0.0) ||
+        !std::isfinite(lu)) {
+      std::printf("mh: uniform(%08x) = %.17g\n", w, u);
+      ++bad;
+    }
+  }
+  float xi[8];
+  hc_mh_xi(r, seed, xi);
+  for (float v : xi)
+    if (!std::isfinite(v) || std::fabs(v) > 6.f) { std::printf("mh: xi %g\n", v); ++bad; }
+  for (int P : {3, 5}) {
+    std::vector<float> L(static_cast<size_t>(P) * P, 0.f), th(P), out(P), prior(2 * static_cast<size_t>(P));
+    for (int p = 0; p < P; ++p) {
+      th[p] = static_cast<float>(uniform(-2.0, 2.0));
+      prior[2 * p] = th[p];
+      prior[2 * p + 1] = 0.5f;
+    }
+    hc_mh_propose(th.data(), L.data(), xi, P, out.data());
+    for (int p = 0; p < P; ++p)
+      if (out[p] != th[p]) { std::printf("mh: zero factor\n"); ++bad; }
+    for (int p = 0; p < P; ++p) L[static_cast<size_t>(p) * P + p] = 1.f;
+    hc_mh_propose(th.data(), L.data(), xi, P, out.data());
+    for (int p = 0; p < P; ++p)
+      if (out[p] != static_cast<float>(static_cast<double>(th[p]) + xi[p])) { std::printf("mh: unit factor\n"); ++bad; }
+    if (hc_mh_log_prior(th.data(), prior.data(), P) != 0.0) { std::printf("mh: log-prior at the mean\n"); ++bad; }
+    prior[0] = th[0] - 1.f;
+    if (hc_mh_log_prior(th.data(), prior.data(), P) != -2.0) { std::printf("mh: log-prior two sd away\n"); ++bad; }
+  }
+  const double inf = INFINITY;
+  if (hc_mh_accept(-1.0, -inf, -3.0, 0.0, 0.0) != 0 || hc_mh_accept(-1.0, -3.0, -inf, 0.0, 0.0) != 1 ||
+      hc_mh_accept(-1.0, -inf, -inf, 0.0, 0.0) != 0 || hc_mh_accept(-1.0, -3.0, -3.0, -0.5, 0.0) != 1 ||
+      hc_mh_accept(-0.5, -3.0, -3.0, -0.5, 0.0) != 0 || hc_mh_accept(-1.0, NAN, -3.0, 0.0, 0.0) != 0) {
+    std::printf("mh: decision\n");
+    ++bad;
+  }
+  return bad;
+}
+
 }  // namespace
 
 int main() {
@@ -811,9 +875,10 @@ int main() {
   bad += check_ps();
   bad += check_gp();
   bad += check_svf();
+  bad += check_mh();
   bad += check_colkey();
   bad += check_select();
-  for (int which = 0; which < 8; ++which) {
+  for (int which = 0; which < 9; ++which) {
     size_t out[2] = {0, 0};
     vissm_host_abi_layout(which, out);
     if (out[0] == 0 || out[1] >= out[0]) { std::printf("abi layout %d: %zu %zu\n", which, out[0], out[1]); ++bad; }

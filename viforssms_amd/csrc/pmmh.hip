@@ -1,0 +1,314 @@
+// libvissm: particle marginal Metropolis-Hastings over theta of the AR, LV and FHN state-space models (vissm_pmmh,
+// include/vissm.h; Andrieu, Doucet & Holenstein 2010).  With the fully adapted filter's unbiased estimate of
+// p(y | theta) in the acceptance ratio the chain targets p(theta | y) exactly, for any number of particles.
+//
+// One block per chain, one particle per lane (N = 64 .. 1024 threads); the block walks its iterations in one launch.
+// An iteration is
+//   the random-walk proposal theta' = theta + L xi and the uniform of the decision (mh_math.hpp), on Philox blocks
+//   whose second counter word is 2;
+//   the fully adapted filter over the whole series at theta', every particle from x_start: the loop of
+//   particle_filter_kernel<MODEL, N, kAdapted> (particle.hip) restated on the same headers (sim_math.hpp,
+//   gp_math.hpp, pf_math.hpp) without the cloud, its tile, the traces, ll_inc and ess -- the same rows, normals,
+//   weights, integers and four barriers per observed step, so ll' is that entry's loglik for K = C filters at
+//   row0 + i C N;
+//   the decision in double, and the chain's outputs from lane 0.
+// Everything outside the filter is block-uniform: every thread computes the proposal, the prior and the decision from
+// the same addresses and the same block sums, so nothing is broadcast and every barrier sits under a block-uniform
+// condition.  A filter that dies (W = 0) leaves its loop at once: ll' = -inf whatever follows.
+//
+// LDS per block = 8 N (C) + 4 S N (gather) + 192 (wave maxima and totals); no tile, so several blocks share a CU up to
+// N = 512.  No atomics, no workspace; integer sums and fixed-order doubles: two launches are bitwise equal and chain
+// c's bits depend on (seed, row0, C, c, N, it0, the data and its entering state) only.
+#include "common.hpp"
+#include "gp_math.hpp"
+#include "mh_math.hpp"
+#include "pf_math.hpp"
+
+namespace vissm {
+namespace pmk {
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+  return v;
+}
+
+// inclusive scan over the wave's 64 lanes
+__device__ __forceinline__ uint64_t wave_scan(uint64_t v, int lane) {
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const uint32_t lo = __shfl_up(static_cast<uint32_t>(v), off, 64);
+    const uint32_t hi = __shfl_up(static_cast<uint32_t>(v >> 32), off, 64);
+    if (lane >= off) v += (static_cast<uint64_t>(hi) << 32) | lo;
+  }
+  return v;
+}
+
+// A block-uniform value the vector ALU computed, moved to a scalar register: the chain's state and the proposal live
+// across the whole filter loop, where the 1024-lane block has no vector registers to spare for them.
+__device__ __forceinline__ float uni(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
+__device__ __forceinline__ uint64_t uni(uint64_t b) {
+  const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(b));
+  const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(b >> 32));
+  return (static_cast<uint64_t>(hi) << 32) | lo;
+}
+__device__ __forceinline__ double uni(double v) {
+  const uint64_t b = __builtin_bit_cast(uint64_t, v);
+  const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(b));
+  const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(b >> 32));
+  return __builtin_bit_cast(double, (static_cast<uint64_t>(hi) << 32) | lo);
+}
+
+struct Out {
+  float* theta_chain;
+  double* ll_chain;
+  int32_t* accept;
+  float* theta_end;
+  double* ll_end;
+  float* theta_prop;
+  double* ll_prop;
+  double* logu;
+};
+
+template <int MODEL, int N>
+__global__ __launch_bounds__(N) void pmmh_kernel(uint64_t seed, uint64_t row0, int C, int n_iter, int it0, int T_total,
+                                                 float dt, float obs_std, const float* __restrict__ theta_cur,
+                                                 const double* __restrict__ ll_cur, const float* __restrict__ prop_chol,
+                                                 const float* __restrict__ prior, const float* __restrict__ x_start,
+                                                 const float* __restrict__ obs, const float* __restrict__ obs_bin,
+                                                 Out o) {
+  constexpr int S = VISSM_MODEL_S(MODEL), P = VISSM_MODEL_P(MODEL);
+  constexpr int NW = N / 64, LOG2N = pf::log2_of(N);
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const size_t c = blockIdx.x;
+
+  __shared__ uint64_t Cs[N];
+  __shared__ float xs[S * N];
+  __shared__ float wmax[16];
+  __shared__ uint64_t wtot[16];
+
+  // the chain's state and the launch's constants: block-uniform
+  float th[mh::kMaxP] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  float x0[S];
+#pragma unroll
+  for (int i = 0; i < P; ++i) th[i] = theta_cur[c * P + i];
+#pragma unroll
+  for (int d = 0; d < S; ++d) x0[d] = x_start[d];
+  double ll = ll_cur[c];
+  double lp = uni(mh::log_prior(th, prior, P));
+  const uint32_t k0 = static_cast<uint32_t>(seed), k1 = static_cast<uint32_t>(seed >> 32);
+  const float R = obs_std * obs_std;
+
+  for (int it = 0; it < n_iter; ++it) {
+    const uint64_t frow = mh::row_of(row0, static_cast<uint64_t>(it0) + it, C, c, N);
+
+    // The factor and the prior are read again in every iteration (scalar loads): held over the filter loop, their
+    // twenty-five doubles would take fifty vector registers, and the 1024-lane FHN block would spill.
+    const float *Lc = prop_chol, *pr = prior;
+    asm volatile("" : "+s"(Lc), "+s"(pr));
+
+    // the proposal
+    float thp[mh::kMaxP] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    {
+      float xi[8], v[4];
+      box_muller4(mh::words(0u, frow, seed), v);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) xi[i] = v[i];
+      box_muller4(mh::words(1u, frow, seed), v);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) xi[4 + i] = v[i];
+      mh::propose(th, Lc, xi, P, thp);
+#pragma unroll
+      for (int i = 0; i < P; ++i) thp[i] = uni(thp[i]);
+    }
+
+    // the fully adapted filter at theta' over steps 0 .. T_total - 1
+    const sim::Par par = sim::prepare<MODEL>(thp, dt);
+    float x[sim::kMaxS] = {0.f, 0.f};
+#pragma unroll
+    for (int d = 0; d < S; ++d) x[d] = x0[d];
+    sim::start<MODEL>(x);
+    double llp = 0.0;
+    const uint64_t row = frow + static_cast<uint64_t>(tid);
+    uint32_t j = 0u, g = 0u;  // stream entry of the step's first normal and its Philox group
+    float cur[4], nxt[4];
+    draw4(g, row, k0, k1, cur);
+    draw4(g + 1, row, k0, k1, nxt);
+
+    for (int ta = 0; ta < T_total; ++ta) {
+      const uint32_t qd = j & 3u;
+      float n[2];
+      if constexpr (S == 2) {
+        n[0] = qd ? cur[2] : cur[0];
+        n[1] = qd ? cur[3] : cur[1];
+      } else {
+        n[0] = qd == 0 ? cur[0] : qd == 1 ? cur[1] : qd == 2 ? cur[2] : cur[3];
+        n[1] = 0.f;
+      }
+      // every thread reads the same addresses: block-uniform
+      float yv[S], bv[S];
+      bool observed = false;
+#pragma unroll
+      for (int d = 0; d < S; ++d) {
+        bv[d] = obs_bin[static_cast<size_t>(d) * T_total + ta];
+        yv[d] = obs[static_cast<size_t>(d) * T_total + ta];
+        observed = observed || bv[d] != 0.f;
+      }
+      if (!observed) {
+        sim::advance<MODEL>(x, par, n, 0.f, nullptr);
+      } else {
+        const bool ok = sim::alive(MODEL, x);
+        const float lw = ok ? gp::state_logw<MODEL>(x, par, yv, bv, R) : -INFINITY;
+        const float wm = wave_max(lw);
+        if (lane == 0) wmax[wid] = wm;
+#pragma unroll
+        for (int d = 0; d < S; ++d) xs[d * N + tid] = x[d];
+        __syncthreads();  // A
+        float m = wmax[0];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) m = fmaxf(m, wmax[w]);
+        m = uni(m);  // the same LDS words in every thread
+        const uint64_t q = pf::quantise(lw, m, ok);
+        const uint64_t cs = wave_scan(q, lane);
+        if (lane == 63) wtot[wid] = cs;
+        __syncthreads();  // B
+        uint64_t before = 0, W = 0;
+#pragma unroll 2
+        for (int w = 0; w < NW; ++w) {
+          if (w < wid) before += wtot[w];
+          W += wtot[w];
+        }
+        Cs[tid] = cs + before;
+        W = uni(W);  // block-uniform: the branches below are scalar
+        __syncthreads();  // C
+        if (W > 0) {
+          const uint32_t U = pf::resample_u(seed, static_cast<uint32_t>(ta), frow);
+          int anc = pf::ancestor(Cs, N, pf::threshold(static_cast<uint32_t>(tid), U, W, LOG2N));
+          anc = min(anc, N - 1);  // tau < W = C[N - 1]: never taken
+#pragma unroll
+          for (int d = 0; d < S; ++d) x[d] = xs[d * N + anc];
+          gp::advance<MODEL>(x, par, yv, bv, R, n);
+          llp = uni(llp + pf::ll_increment(m, W, N));
+        } else {  // no live particle with a weight: the proposal is dead
+          llp = -INFINITY;
+        }
+        __syncthreads();  // D: the gather is over before the next observed step overwrites the staging arrays
+        if (W == 0) break;
+      }
+      j += S;
+      if ((j & 3u) == 0u) {  // uniform: the next step opens a new group; draw the one after it now
+#pragma unroll
+        for (int i = 0; i < 4; ++i) cur[i] = nxt[i];
+        ++g;
+        draw4(g + 1, row, k0, k1, nxt);
+      }
+    }
+
+    // the decision (its uniform and the proposal's prior are not needed before: they are not kept over the filter)
+    const double lpp = mh::log_prior(thp, pr, P);
+    const double logu = mh::log_uniform(mh::words(2u, frow, seed).x);
+    const bool acc = __builtin_amdgcn_readfirstlane(mh::accept(logu, llp, ll, lpp, lp) ? 1 : 0) != 0;
+    if (acc) {
+#pragma unroll
+      for (int i = 0; i < P; ++i) th[i] = thp[i];
+      ll = uni(llp);
+      lp = uni(lpp);
+    }
+    if (tid == 0) {
+      const size_t e = c * static_cast<size_t>(n_iter) + it;
+#pragma unroll
+      for (int i = 0; i < P; ++i) o.theta_chain[e * P + i] = th[i];
+      o.ll_chain[e] = ll;
+      o.accept[e] = acc ? 1 : 0;
+      if (o.theta_prop) {
+#pragma unroll
+        for (int i = 0; i < P; ++i) o.theta_prop[e * P + i] = thp[i];
+      }
+      if (o.ll_prop) o.ll_prop[e] = llp;
+      if (o.logu) o.logu[e] = logu;
+    }
+  }
+  if (tid == 0) {
+#pragma unroll
+    for (int i = 0; i < P; ++i) o.theta_end[c * P + i] = th[i];
+    o.ll_end[c] = ll;
+  }
+}
+
+struct Args {
+  const VissmPmmhDesc* d;
+  uint64_t seed, row0;
+  const float* theta_cur;
+  const double* ll_cur;
+  const float *prop_chol, *prior, *x_start, *obs, *obs_bin;
+  Out o;
+  hipStream_t st;
+};
+
+template <int MODEL, int N>
+void launch(const Args& a) {
+  hipLaunchKernelGGL((pmmh_kernel<MODEL, N>), dim3(a.d->C), dim3(N), 0, a.st, a.seed, a.row0, a.d->C, a.d->n_iter,
+                     a.d->it0, a.d->T_total, a.d->dt, a.d->obs_std, a.theta_cur, a.ll_cur, a.prop_chol, a.prior,
+                     a.x_start, a.obs, a.obs_bin, a.o);
+}
+
+template <int MODEL>
+void launch_n(const Args& a) {
+  switch (a.d->N) {
+    case 64: launch<MODEL, 64>(a); break;
+    case 128: launch<MODEL, 128>(a); break;
+    case 256: launch<MODEL, 256>(a); break;
+    case 512: launch<MODEL, 512>(a); break;
+    default: launch<MODEL, 1024>(a); break;
+  }
+}
+
+}  // namespace pmk
+}  // namespace vissm
+
+using namespace vissm;
+using namespace vissm::pmk;
+
+extern "C" int32_t vissm_pmmh_lds_bytes(int32_t model, int32_t N) {
+  if (!(model == VISSM_MODEL_AR || model == VISSM_MODEL_LV || model == VISSM_MODEL_FHN) || !pf::valid_n(N)) return 0;
+  return 8 * N + 4 * VISSM_MODEL_S(model) * N + 16 * (4 + 8);
+}
+
+extern "C" int vissm_pmmh(const VissmPmmhDesc* d, uint64_t seed, uint64_t row0, const float* theta_cur,
+                          const double* ll_cur, const float* prop_chol, const float* prior, const float* x_start,
+                          const float* obs, const float* obs_bin, float* theta_chain, double* ll_chain,
+                          int32_t* accept, float* theta_end, double* ll_end, float* theta_prop, double* ll_prop,
+                          double* logu, void* stream) {
+  // host arithmetic only, before any GPU call
+  VISSM_CHECK_ARG(d, "pmmh: null descriptor");
+  VISSM_CHECK_ARG(d->model != VISSM_MODEL_SV,
+                  "pmmh: no observation model for SV (its first coordinate is the observed series)");
+  VISSM_CHECK_ARG(d->model == VISSM_MODEL_AR || d->model == VISSM_MODEL_LV || d->model == VISSM_MODEL_FHN,
+                  "pmmh: unknown model %d", d->model);
+  VISSM_CHECK_ARG(pf::valid_n(d->N), "pmmh: N=%d particles (64, 128, 256, 512 or 1024)", d->N);
+  VISSM_CHECK_ARG(d->C >= 1, "pmmh: C=%d chains (at least one)", d->C);
+  VISSM_CHECK_ARG(d->n_iter >= 0 && d->it0 >= 0 && static_cast<int64_t>(d->it0) + d->n_iter < (int64_t{1} << 31),
+                  "pmmh: bad iterations it0=%d n_iter=%d", d->it0, d->n_iter);
+  VISSM_CHECK_ARG(d->T_total >= 0, "pmmh: T_total=%d", d->T_total);
+  const int S = VISSM_MODEL_S(d->model);
+  VISSM_CHECK_ARG(static_cast<int64_t>(d->T_total) * S < (int64_t{1} << 31), "pmmh: T_total S = %d %d reaches 2^31",
+                  d->T_total, S);
+  // (a NaN fails the first comparison, an infinity the second)
+  VISSM_CHECK_ARG(d->obs_std > 0.f && d->obs_std <= 3.4028234e38f,
+                  "pmmh: a positive, finite obs_std expected, got %g", static_cast<double>(d->obs_std));
+  VISSM_CHECK_ARG(theta_cur && ll_cur && prop_chol && prior && x_start && theta_end && ll_end, "pmmh: null pointer");
+  VISSM_CHECK_ARG(d->n_iter == 0 || (theta_chain && ll_chain && accept), "pmmh: null pointer (n_iter > 0)");
+  VISSM_CHECK_ARG(d->T_total == 0 || (obs && obs_bin), "pmmh: null pointer (T_total > 0)");
+  const Args a{d,   seed,    row0, theta_cur, ll_cur, prop_chol, prior,
+               x_start, obs, obs_bin,
+               Out{theta_chain, ll_chain, accept, theta_end, ll_end, theta_prop, ll_prop, logu}, as_stream(stream)};
+  switch (d->model) {
+    case VISSM_MODEL_AR: launch_n<VISSM_MODEL_AR>(a); break;
+    case VISSM_MODEL_LV: launch_n<VISSM_MODEL_LV>(a); break;
+    default: launch_n<VISSM_MODEL_FHN>(a); break;
+  }
+  VISSM_CHECK_LAUNCH("pmmh");
+  return VISSM_OK;
+}

@@ -1250,3 +1250,83 @@ def sv_smooth(theta: torch.Tensor, cloud: torch.Tensor, obs: torch.Tensor, dt: f
                                       ptr(x_next), ptr(paths), ptr(x_first), ptr(ix), ptr(qt),
                                       _lib.stream_handle(dev)), "vissm_sv_smooth")
     return ParticleSmoothResult(paths, x_first, ix, qt)
+
+
+# ---------------------------------------------------------------------------------------
+# particle marginal Metropolis-Hastings (the theta posterior p(theta | y))
+# ---------------------------------------------------------------------------------------
+@dataclass
+class PmmhResult:
+    theta_chain: torch.Tensor            # [C, n_iter, P] the chain's state after each decision
+    ll_chain: torch.Tensor               # [C, n_iter] float64, its log-evidence estimate
+    accept: torch.Tensor                 # [C, n_iter] int32
+    theta_end: torch.Tensor              # [C, P]: theta_cur of the call that continues at it0 + n_iter
+    ll_end: torch.Tensor                 # [C] float64: its ll_cur
+    theta_prop: Optional[torch.Tensor]   # [C, n_iter, P] the proposals, or None
+    ll_prop: Optional[torch.Tensor]      # [C, n_iter] float64 their estimates (-inf: a dead filter), or None
+    logu: Optional[torch.Tensor]         # [C, n_iter] float64 the logs of the decisions' uniforms, or None
+
+
+def pmmh(model_id: int, theta_cur: torch.Tensor, ll_cur: torch.Tensor, prop_chol: torch.Tensor, prior: torch.Tensor,
+         x_start: torch.Tensor, obs: torch.Tensor, obs_bin: torch.Tensor, dt: float, obs_std: float, N: int,
+         n_iter: int, seed: int, row0: int, it0: int = 0, trace: bool = False) -> PmmhResult:
+    """n_iter iterations of C particle marginal Metropolis-Hastings chains, one per row of theta_cur [C, P] (raw, as
+    the ELBO takes it); vissm_pmmh: one block per chain, the whole chain in one launch.  An iteration proposes
+    theta' = theta + L xi with prop_chol = L [P, P] (lower), estimates log p(y | theta') with the fully adapted filter
+    of N particles over obs / obs_bin [S, T] from x_start [S], and accepts iff log u < (ll' - ll) + (lp' - lp), lp the
+    independent Gaussian log-prior of prior [P, 2] = (mean, sd).  ll_cur [C] float64 is the estimate that goes with
+    theta_cur: particle_filter(proposal="adapted", cloud=False).loglik.  Iteration i of chain c uses the Philox rows
+    row0 + (i C + c) N .. + N - 1: its filter is particle_filter's for K = C at row0 + i C N, its proposal and uniform
+    sit on counter word 1 = 2 of the first of them.  A call with it0' = it0 + n_iter, theta_cur = theta_end and ll_cur =
+    ll_end continues bitwise.  trace: also the proposals, their estimates and log u.  AR, LV and FHN."""
+    # the refusals of the C entry, by host arithmetic before any GPU call
+    if model_id == _lib.MODEL_SV:
+        raise ValueError("pmmh: no observation model for SV (its first coordinate is the observed series)")
+    if model_id not in _lib.MODEL_S:
+        raise ValueError(f"pmmh: unknown model {model_id}")
+    S, P = _lib.MODEL_S[model_id], _lib.MODEL_P[model_id]
+    N, n_iter, it0 = int(N), int(n_iter), int(it0)
+    if N not in _lib.PF_PARTICLES:
+        raise ValueError(f"pmmh: N={N} particles, one of {_lib.PF_PARTICLES} expected")
+    if not 0.0 < float(obs_std) < float("inf"):
+        raise ValueError(f"pmmh: a positive, finite obs_std expected, got {obs_std}")
+    if theta_cur.dim() != 2 or theta_cur.shape[1] != P or theta_cur.shape[0] < 1:
+        raise ValueError(f"pmmh: theta_cur [C >= 1, {P}] expected, got {tuple(theta_cur.shape)}")
+    C = theta_cur.shape[0]
+    if n_iter < 0 or it0 < 0 or it0 + n_iter >= 2 ** 31:
+        raise ValueError(f"pmmh: bad iterations it0={it0} n_iter={n_iter}")
+    if obs.dim() != 2 or obs.shape[0] != S or obs_bin.shape != obs.shape:
+        raise ValueError(f"pmmh: obs and obs_bin [{S}, T] expected, got {tuple(obs.shape)} and "
+                         f"{tuple(obs_bin.shape)}")
+    T_total = obs.shape[1]
+    if T_total * S >= 2 ** 31:
+        raise ValueError(f"pmmh: T S = {T_total} * {S} reaches 2^31")
+    if not 0 <= int(row0) < 2 ** 64:
+        raise ValueError(f"pmmh: row0={row0} outside [0, 2^64)")
+    _require_gpu(theta_cur, prop_chol, prior, x_start, obs, obs_bin)
+    for name, t, shape in (("theta_cur", theta_cur, (C, P)), ("prop_chol", prop_chol, (P, P)),
+                           ("prior", prior, (P, 2)), ("x_start", x_start, (S,)), ("obs", obs, (S, T_total)),
+                           ("obs_bin", obs_bin, (S, T_total))):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape:
+            raise ValueError(f"pmmh: fp32 {name} {list(shape)} expected, got {t.dtype} {tuple(t.shape)}")
+    dev = theta_cur.device
+    if not ll_cur.is_cuda or ll_cur.dtype != torch.float64 or tuple(ll_cur.shape) != (C,) or \
+            not ll_cur.is_contiguous():
+        raise ValueError(f"pmmh: ll_cur: a contiguous float64 GPU tensor [{C}] expected")
+    if any(t.device != dev for t in (ll_cur, prop_chol, prior, x_start, obs, obs_bin)):
+        raise ValueError("pmmh: all tensors on one device expected")
+    key, row = ctypes.c_uint64(seed & (2 ** 64 - 1)), ctypes.c_uint64(int(row0))
+    theta_chain = torch.empty(C, n_iter, P, dtype=torch.float32, device=dev)
+    ll_chain = torch.empty(C, n_iter, dtype=torch.float64, device=dev)
+    accept = torch.empty(C, n_iter, dtype=torch.int32, device=dev)
+    theta_end = torch.empty(C, P, dtype=torch.float32, device=dev)
+    ll_end = torch.empty(C, dtype=torch.float64, device=dev)
+    tp = torch.empty(C, n_iter, P, dtype=torch.float32, device=dev) if trace else None
+    lpr = torch.empty(C, n_iter, dtype=torch.float64, device=dev) if trace else None
+    lu = torch.empty(C, n_iter, dtype=torch.float64, device=dev) if trace else None
+    d = _lib.PmmhDesc(model_id, C, N, n_iter, it0, T_total, float(dt), float(obs_std))
+    check(_lib.load().vissm_pmmh(ctypes.byref(d), key, row, ptr(theta_cur), ptr(ll_cur), ptr(prop_chol), ptr(prior),
+                                 ptr(x_start), ptr(obs), ptr(obs_bin), ptr(theta_chain), ptr(ll_chain), ptr(accept),
+                                 ptr(theta_end), ptr(ll_end), ptr(tp), ptr(lpr), ptr(lu), _lib.stream_handle(dev)),
+          "vissm_pmmh")
+    return PmmhResult(theta_chain, ll_chain, accept, theta_end, ll_end, tp, lpr, lu)
