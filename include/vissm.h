@@ -832,6 +832,41 @@ int vissm_pmmh(const VissmPmmhDesc* d, uint64_t seed, uint64_t row0,
                double* logu /* [C][n_iter] or NULL */, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Particle marginal Metropolis-Hastings over theta of the stochastic-volatility model, which vissm_pmmh refuses for
+ * want of an obs_std / obs_bin observation model: the same chains around vissm_sv_filter's filter, which is exactly
+ * fully adapted, so each chain targets p(theta | y) exactly for any N.  VissmPmmhDesc with model = VISSM_MODEL_SV
+ * (anything else is refused), obs_std ignored; P = 4.  One block per chain, N particles (the filter's five sizes), the
+ * chain's n_iter iterations inside one launch.  Chain c runs the absolute iterations i = it0 .. it0 + n_iter - 1; with
+ * r = row0 + (i C + c) N (csrc/mh_math.hpp):
+ *   words, theta', lp(theta) and the decision are vissm_pmmh's, unchanged, with P = 4: the proposal's and the
+ *           uniform's Philox blocks carry 2 in the second counter word, the filter's normals 0 and its resampling
+ *           integers 1
+ *   ll' = the loglik vissm_sv_filter gives for K = C, row0' = row0 + i C N, t0 = 0, H = T_total, theta_c = theta',
+ *           every particle started at h_start[0] (not finite: the quiet NaN, a dead filter), over the series obs of
+ *           T_total + 1 values: the same rows, normals, weights and resampling integers.  A filter that dies (W = 0; a
+ *           zero in y[0 .. T_total - 1] kills it through NaN weights) gives ll' = -inf.
+ *   accept iff log(u) < (ll' - ll) + (lp' - lp), in double: vissm_pmmh's rule and its -inf and NaN cases.
+ * ll_cur [C] is required: the estimate that goes with theta_cur (vissm_sv_filter with cloud = NULL).
+ *
+ * Outputs, chaining through theta_end / ll_end and it0, the optional traces and reproducibility are vissm_pmmh's.  No
+ * atomics, no workspace; two launches are bitwise equal.  Refused by host arithmetic (VISSM_EINVAL): a null
+ * descriptor, a model other than SV, N not one of the five, C < 1, n_iter < 0, it0 < 0, it0 + n_iter >= 2^31,
+ * T_total < 0 or >= 2^31 - 1, dt not positive and finite, a null pointer (obs may be NULL only if T_total = 0;
+ * theta_chain, ll_chain and accept only if n_iter = 0).
+ * vissm_sv_pmmh_lds_bytes: the LDS one block declares, 8 N + 4 N + 192 (host arithmetic; 0 = bad N).
+ * ------------------------------------------------------------------------- */
+int32_t vissm_sv_pmmh_lds_bytes(int32_t N);
+int vissm_sv_pmmh(const VissmPmmhDesc* d, uint64_t seed, uint64_t row0,
+                  const float* theta_cur /* [C][4] */, const double* ll_cur /* [C] */,
+                  const float* prop_chol /* [4][4] lower */, const float* prior /* [4][2] (mean, sd) */,
+                  const float* h_start /* [1]: h at step 0, every particle starts there */,
+                  const float* obs /* y[0 .. T_total]: T_total + 1 values */,
+                  float* theta_chain /* [C][n_iter][4] */, double* ll_chain /* [C][n_iter] */,
+                  int32_t* accept /* [C][n_iter] */, float* theta_end /* [C][4] */, double* ll_end /* [C] */,
+                  float* theta_prop /* [C][n_iter][4] or NULL */, double* ll_prop /* [C][n_iter] or NULL */,
+                  double* logu /* [C][n_iter] or NULL */, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Opt-in kernel timing (for bench.py's live roofline): when enabled, the flow
  * entry points bracket their main kernel with hipEvents on the launch stream.
  * kind: VISSM_PROF_FLOW_FWD / VISSM_PROF_FLOW_BWD (flow kernels),

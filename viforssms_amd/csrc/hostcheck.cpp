@@ -6,7 +6,8 @@
 // of ps_math.hpp (the particle smoother's backward weights and integer selection) against float64 and big ints,
 // of gp_math.hpp (the adapted filter's predictive weight and conditional draw) against numpy.linalg in float64,
 // of svf_math.hpp (the stochastic-volatility filter's weight and move, the smoother's pair weight) against float64,
-// and of mh_math.hpp (the Metropolis-Hastings chain's words, proposal, log-prior and acceptance rule) against numpy.
+// of mh_math.hpp (the Metropolis-Hastings chain's words, proposal, log-prior and acceptance rule) against numpy,
+// and one whole iteration of the stochastic-volatility chain, run serially on mh_math.hpp and svf_math.hpp.
 // Not part of the product path: libvissm_hostcheck.so is loaded only by tests/.
 #include <cstddef>
 
@@ -286,6 +287,69 @@ void hc_mh_propose(const float* th, const float* L, const float* xi, int P, floa
 double hc_mh_log_prior(const float* th, const float* prior, int P) { return vissm::mh::log_prior(th, prior, P); }
 int hc_mh_accept(double logu, double ll_prop, double ll_cur, double lp_prop, double lp_cur) {
   return vissm::mh::accept(logu, ll_prop, ll_cur, lp_prop, lp_cur) ? 1 : 0;
+}
+
+// One iteration of one stochastic-volatility chain (sv_pmmh_kernel's, pmmh.hip) run serially on mh_math.hpp and
+// svf::filter_step: iteration i of chain c of C with n particles from the state theta [4] with the estimate ll_cur.
+// The proposal's normals come from box_muller4_ref, the filter's from the same formula on the Philox counter
+// (ta / 4, 0, lo32(row), hi32(row)), entry ta % 4, of row = r + lane; the resampling integer is pf::resample_u(seed, ta,
+// r).  The filter starts every particle at h_start (not finite: the quiet NaN) over y [T + 1] and leaves at W = 0 with
+// ll' = -inf.  theta_prop [4]; out = {lp, lp', log u, ll'}; optional traces: h_tr [T + 1][n] the states before each step
+// and after the last, q_tr and anc_tr [T][n], n_tr [T][n] the normals, m_tr and W_tr [T] (rows past a death are left
+// untouched).  Returns the decision.
+int hc_svpmmh_iteration(uint64_t seed, uint64_t row0, uint64_t i, uint64_t C, uint64_t c, int n, int T, float dt,
+                        const float* theta, double ll_cur, const float* L, const float* prior, float h_start,
+                        const float* y, float* theta_prop, double* out, float* h_tr, uint64_t* q_tr, int32_t* anc_tr,
+                        float* n_tr, float* m_tr, uint64_t* W_tr) {
+  using namespace vissm;
+  constexpr int P = VISSM_MODEL_P(VISSM_MODEL_SV);
+  if (n < 1 || n > pf::kMaxN || T < 0) return -1;
+  const uint64_t r = mh::row_of(row0, i, C, c, static_cast<uint64_t>(n));
+  float xi[8];
+  mh::box_muller4_ref(mh::words(0u, r, seed), xi);
+  mh::box_muller4_ref(mh::words(1u, r, seed), xi + 4);
+  mh::propose(theta, L, xi, P, theta_prop);
+  const uint32_t k0 = static_cast<uint32_t>(seed), k1 = static_cast<uint32_t>(seed >> 32);
+  float h[pf::kMaxN], hn[pf::kMaxN], nn[pf::kMaxN];
+  uint64_t q[pf::kMaxN], Cs[pf::kMaxN];
+  int32_t anc[pf::kMaxN];
+  for (int p = 0; p < n; ++p) h[p] = __builtin_isfinite(h_start) ? h_start : sim::quiet_nan();
+  double llp = 0.0;
+  for (int ta = 0; ta < T; ++ta) {
+    for (int p = 0; p < n; ++p) {
+      const uint64_t row = r + static_cast<uint64_t>(p);
+      const u4 ctr{static_cast<uint32_t>(ta) >> 2, 0u, static_cast<uint32_t>(row), static_cast<uint32_t>(row >> 32)};
+      float v[4];
+      mh::box_muller4_ref(philox4x32_10(ctr, k0, k1), v);
+      nn[p] = v[ta & 3];
+    }
+    float m = 0.f;
+    const uint64_t W = svf::filter_step(h, n, theta_prop, dt, y[ta], y[ta + 1], nn,
+                                        pf::resample_u(seed, static_cast<uint32_t>(ta), r), hn, q, anc, Cs, &m);
+    const size_t o = static_cast<size_t>(ta) * n;
+    for (int p = 0; p < n; ++p) {
+      if (h_tr) h_tr[o + p] = h[p];
+      if (q_tr) q_tr[o + p] = q[p];
+      if (anc_tr) anc_tr[o + p] = W ? anc[p] : -1;
+      if (n_tr) n_tr[o + p] = nn[p];
+      if (h_tr) h_tr[o + n + p] = hn[p];
+      h[p] = hn[p];
+    }
+    if (m_tr) m_tr[ta] = m;
+    if (W_tr) W_tr[ta] = W;
+    if (W == 0) {
+      llp = -__builtin_inf();
+      break;
+    }
+    llp += pf::ll_increment(m, W, n);
+  }
+  const double lp = mh::log_prior(theta, prior, P), lpp = mh::log_prior(theta_prop, prior, P);
+  const double logu = mh::log_uniform(mh::words(2u, r, seed).x);
+  out[0] = lp;
+  out[1] = lpp;
+  out[2] = logu;
+  out[3] = llp;
+  return mh::accept(logu, llp, ll_cur, lpp, lp) ? 1 : 0;
 }
 
 // the C ABI's struct layouts as the C compiler sees them (the ctypes mirrors in viforssms_amd/_lib.py are

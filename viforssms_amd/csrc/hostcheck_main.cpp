@@ -19,6 +19,8 @@
 // restatement, sim_math.hpp's own SV step and sv_trans' joint density, with whole serial steps and draws;
 // the Metropolis-Hastings chain's words, uniform, proposal, log-prior and acceptance rule (mh_math.hpp) on their edge
 // cases: the counter's second word, u inside (0, 1), a zero factor, the -inf and NaN decisions;
+// whole iterations of the stochastic-volatility chain run serially (hc_svpmmh_iteration): a zero factor proposes theta
+// itself, the traces rebuild ll', a zero in the series and a state that is not finite kill the proposal;
 // any sanitizer report aborts the run (-fno-sanitize-recover=all).
 // Exit 0 = all checks passed.  Not part of the product path.
 #include <cmath>
@@ -80,6 +82,10 @@ void hc_mh_xi(uint64_t r, uint64_t seed, float out[8]);
 void hc_mh_propose(const float* th, const float* L, const float* xi, int P, float* out);
 double hc_mh_log_prior(const float* th, const float* prior, int P);
 int hc_mh_accept(double logu, double ll_prop, double ll_cur, double lp_prop, double lp_cur);
+int hc_svpmmh_iteration(uint64_t seed, uint64_t row0, uint64_t i, uint64_t C, uint64_t c, int n, int T, float dt,
+                        const float* theta, double ll_cur, const float* L, const float* prior, float h_start,
+                        const float* y, float* theta_prop, double* out, float* h_tr, uint64_t* q_tr, int32_t* anc_tr,
+                        float* n_tr, float* m_tr, uint64_t* W_tr);
 }
 
 namespace {
@@ -849,6 +855,66 @@ int check_mh() {
   return bad;
 }
 
+// hc_svpmmh_iteration: with a zero factor the proposal is theta itself and lp' = lp; ll' is the sum of the traced
+// increments; every traced ancestor is in range and every new state the move of its ancestor's; a chain at -inf accepts
+// a live proposal; a zero in the series, a start that is not finite and T = 0 behave as the kernel's text says
+int check_svpmmh() {
+  int bad = 0;
+  const uint64_t seed = 0x0BADC0FFEE123457ull;
+  const float th[4] = {0.001f, -0.6f, -2.5257287f, -0.6931472f};
+  const float prior[8] = {0.001f, 0.05f, -0.6f, 0.2f, -2.5f, 0.3f, -0.7f, 0.3f};
+  for (int n : {64, 128}) {
+    for (int T : {0, 1, 5, 9}) {
+      std::vector<float> y(static_cast<size_t>(T) + 1), L(16, 0.f), h_tr(static_cast<size_t>(T + 1) * n),
+          n_tr(static_cast<size_t>(T) * n + 1), m_tr(T + 1);
+      std::vector<uint64_t> q_tr(static_cast<size_t>(T) * n + 1), W_tr(T + 1);
+      std::vector<int32_t> anc_tr(static_cast<size_t>(T) * n + 1);
+      y[0] = 5.f;
+      for (int t = 0; t < T; ++t) y[t + 1] = y[t] * (1.f + 0.02f * static_cast<float>(uniform(-1.0, 1.0)));
+      float thp[4];
+      double out[4];
+      int acc = hc_svpmmh_iteration(seed, 1000, 3, 5, 2, n, T, 1.f, th, -INFINITY, L.data(), prior, -8.5f, y.data(), thp,
+                                    out, h_tr.data(), q_tr.data(), anc_tr.data(), n_tr.data(), m_tr.data(), W_tr.data());
+      if (std::memcmp(thp, th, sizeof thp) != 0 || out[0] != out[1]) { std::printf("svpmmh: zero factor\n"); ++bad; }
+      if (!(out[2] < 0.0) || !std::isfinite(out[3]) || acc != 1) {
+        std::printf("svpmmh: n=%d T=%d ll'=%g acc=%d\n", n, T, out[3], acc);
+        ++bad;
+      }
+      double ll = 0.0;
+      for (int t = 0; t < T; ++t) {
+        ll += static_cast<double>(m_tr[t]) + std::log(static_cast<double>(W_tr[t])) - 40.0 * std::log(2.0) -
+              std::log(static_cast<double>(n));
+        for (int p = 0; p < n; ++p) {
+          const size_t o = static_cast<size_t>(t) * n;
+          const int a = anc_tr[o + p];
+          if (a < 0 || a >= n) { std::printf("svpmmh: ancestor %d\n", a); ++bad; continue; }
+          const float want = hc_svf_move(h_tr[o + a], thp, 1.f, n_tr[o + p]);
+          if (std::memcmp(&want, &h_tr[o + n + p], sizeof want) != 0) { std::printf("svpmmh: move\n"); ++bad; }
+        }
+      }
+      if (std::fabs(ll - out[3]) > 1e-9) { std::printf("svpmmh: ll' %.17g against %.17g\n", out[3], ll); ++bad; }
+      // against itself the same finite proposal is accepted iff log u < 0: always
+      if (hc_svpmmh_iteration(seed, 1000, 3, 5, 2, n, T, 1.f, th, out[3], L.data(), prior, -8.5f, y.data(), thp, out,
+                              nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) != 1) {
+        std::printf("svpmmh: equal estimates\n");
+        ++bad;
+      }
+      if (T >= 5) {
+        y[2] = 0.f;  // step 2 divides by it: NaN weights, W = 0
+        acc = hc_svpmmh_iteration(seed, 1000, 3, 5, 2, n, T, 1.f, th, -3.0, L.data(), prior, -8.5f, y.data(), thp, out,
+                                  nullptr, nullptr, nullptr, nullptr, nullptr, W_tr.data());
+        if (acc != 0 || out[3] != -INFINITY || W_tr[2] != 0) { std::printf("svpmmh: a zero in y\n"); ++bad; }
+      }
+      if (T >= 1) {
+        acc = hc_svpmmh_iteration(seed, 1000, 3, 5, 2, n, T, 1.f, th, -INFINITY, L.data(), prior, NAN, y.data(), thp, out,
+                                  nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+        if (acc != 0 || out[3] != -INFINITY) { std::printf("svpmmh: a NaN start\n"); ++bad; }
+      }
+    }
+  }
+  return bad;
+}
+
 }  // namespace
 
 int main() {
@@ -876,6 +942,7 @@ int main() {
   bad += check_gp();
   bad += check_svf();
   bad += check_mh();
+  bad += check_svpmmh();
   bad += check_colkey();
   bad += check_select();
   for (int which = 0; which < 9; ++which) {

@@ -19,10 +19,14 @@
 // LDS per block = 8 N (C) + 4 S N (gather) + 192 (wave maxima and totals); no tile, so several blocks share a CU up to
 // N = 512.  No atomics, no workspace; integer sums and fixed-order doubles: two launches are bitwise equal and chain
 // c's bits depend on (seed, row0, C, c, N, it0, the data and its entering state) only.
+//
+// The stochastic-volatility model has no obs_std / obs_bin observation model and vissm_pmmh refuses it; vissm_sv_pmmh
+// (sv_pmmh_kernel, below) runs the same chain around sv_filter.hip's filter of the latent log-volatility.
 #include "common.hpp"
 #include "gp_math.hpp"
 #include "mh_math.hpp"
 #include "pf_math.hpp"
+#include "svf_math.hpp"
 
 namespace vissm {
 namespace pmk {
@@ -265,6 +269,170 @@ void launch_n(const Args& a) {
   }
 }
 
+// ---- stochastic volatility ----------------------------------------------------------------------------------------
+// The same iteration shell around sv_filter_kernel's loop (sv_filter.hip) with t0 = 0 and H = T_total: the particle is
+// the latent h alone, the observed series y [T_total + 1] the state's first coordinate.  Every step is observed: step
+// ta scores the pre-step h on (y[ta], y[ta + 1]), resamples and moves the ancestor's h with the lane's own normal
+// (AR's one-normal stream), so ll' is vissm_sv_filter's loglik for K = C filters at row0 + i C N from h_start.  The
+// shell is restated here, not shared with pmmh_kernel as a device function: that kernel's assembly stays what it was.
+// LDS per block = 8 N (C) + 4 N (gather) + 192.
+constexpr int kSvP = VISSM_MODEL_P(VISSM_MODEL_SV);
+
+template <int N>
+__global__ __launch_bounds__(N) void sv_pmmh_kernel(uint64_t seed, uint64_t row0, int C, int n_iter, int it0,
+                                                    int T_total, float dt, const float* __restrict__ theta_cur,
+                                                    const double* __restrict__ ll_cur,
+                                                    const float* __restrict__ prop_chol,
+                                                    const float* __restrict__ prior, const float* __restrict__ h_start,
+                                                    const float* __restrict__ obs, Out o) {
+  constexpr int P = kSvP;
+  constexpr int NW = N / 64, LOG2N = pf::log2_of(N);
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const size_t c = blockIdx.x;
+
+  __shared__ uint64_t Cs[N];
+  __shared__ float xs[N];
+  __shared__ float wmax[16];
+  __shared__ uint64_t wtot[16];
+
+  // the chain's state and the launch's constants: block-uniform
+  float th[mh::kMaxP] = {0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int i = 0; i < P; ++i) th[i] = theta_cur[c * P + i];
+  float h0 = h_start[0];
+  if (!__builtin_isfinite(h0)) h0 = sim::quiet_nan();
+  double ll = ll_cur[c];
+  double lp = uni(mh::log_prior(th, prior, P));
+  const uint32_t k0 = static_cast<uint32_t>(seed), k1 = static_cast<uint32_t>(seed >> 32);
+
+  for (int it = 0; it < n_iter; ++it) {
+    const uint64_t frow = mh::row_of(row0, static_cast<uint64_t>(it0) + it, C, c, N);
+
+    // the factor and the prior are read again in every iteration (scalar loads), as pmmh_kernel reads them
+    const float *Lc = prop_chol, *pr = prior;
+    asm volatile("" : "+s"(Lc), "+s"(pr));
+
+    // the proposal
+    float thp[mh::kMaxP] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    {
+      float xi[8], v[4];
+      box_muller4(mh::words(0u, frow, seed), v);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) xi[i] = v[i];
+      box_muller4(mh::words(1u, frow, seed), v);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) xi[4 + i] = v[i];
+      mh::propose(th, Lc, xi, P, thp);
+#pragma unroll
+      for (int i = 0; i < P; ++i) thp[i] = uni(thp[i]);
+    }
+
+    // the filter at theta' over steps 0 .. T_total - 1
+    const sim::Par par = sim::prepare<VISSM_MODEL_SV>(thp, dt);
+    float h = h0;
+    double llp = 0.0;
+    const uint64_t row = frow + static_cast<uint64_t>(tid);
+    uint32_t j = 0u, g = 0u;  // stream entry of the step's normal and its Philox group
+    float cur[4], nxt[4];
+    draw4(g, row, k0, k1, cur);
+    draw4(g + 1, row, k0, k1, nxt);
+
+    for (int ta = 0; ta < T_total; ++ta) {
+      const uint32_t qd = j & 3u;
+      const float n = qd == 0 ? cur[0] : qd == 1 ? cur[1] : qd == 2 ? cur[2] : cur[3];
+      // every thread reads the same addresses: block-uniform
+      const svf::Obs ob = svf::obs_prep(obs[ta], obs[static_cast<size_t>(ta) + 1], par);
+      const bool ok = __builtin_isfinite(h);
+      const float lw = svf::state_logw(h, ob);
+      const float wm = wave_max(lw);
+      if (lane == 0) wmax[wid] = wm;
+      xs[tid] = h;
+      __syncthreads();  // A
+      float m = wmax[0];
+#pragma unroll
+      for (int w = 1; w < NW; ++w) m = fmaxf(m, wmax[w]);
+      m = uni(m);  // the same LDS words in every thread
+      const uint64_t q = pf::quantise(lw, m, ok);
+      const uint64_t cs = wave_scan(q, lane);
+      if (lane == 63) wtot[wid] = cs;
+      __syncthreads();  // B
+      uint64_t before = 0, W = 0;
+#pragma unroll 2
+      for (int w = 0; w < NW; ++w) {
+        if (w < wid) before += wtot[w];
+        W += wtot[w];
+      }
+      Cs[tid] = cs + before;
+      W = uni(W);  // block-uniform: the branches below are scalar
+      __syncthreads();  // C
+      if (W > 0) {
+        const uint32_t U = pf::resample_u(seed, static_cast<uint32_t>(ta), frow);
+        int anc = pf::ancestor(Cs, N, pf::threshold(static_cast<uint32_t>(tid), U, W, LOG2N));
+        anc = min(anc, N - 1);  // tau < W = C[N - 1]: never taken
+        h = svf::move(xs[anc], par, n);
+        llp = uni(llp + pf::ll_increment(m, W, N));
+      } else {  // no live particle with a weight (a zero in y gives NaN weights): the proposal is dead
+        llp = -INFINITY;
+      }
+      __syncthreads();  // D: the gather is over before the next step overwrites the staging arrays
+      if (W == 0) break;
+      ++j;
+      if ((j & 3u) == 0u) {  // uniform: the next step opens a new group; draw the one after it now
+#pragma unroll
+        for (int i = 0; i < 4; ++i) cur[i] = nxt[i];
+        ++g;
+        draw4(g + 1, row, k0, k1, nxt);
+      }
+    }
+
+    // the decision
+    const double lpp = mh::log_prior(thp, pr, P);
+    const double logu = mh::log_uniform(mh::words(2u, frow, seed).x);
+    const bool acc = __builtin_amdgcn_readfirstlane(mh::accept(logu, llp, ll, lpp, lp) ? 1 : 0) != 0;
+    if (acc) {
+#pragma unroll
+      for (int i = 0; i < P; ++i) th[i] = thp[i];
+      ll = uni(llp);
+      lp = uni(lpp);
+    }
+    if (tid == 0) {
+      const size_t e = c * static_cast<size_t>(n_iter) + it;
+#pragma unroll
+      for (int i = 0; i < P; ++i) o.theta_chain[e * P + i] = th[i];
+      o.ll_chain[e] = ll;
+      o.accept[e] = acc ? 1 : 0;
+      if (o.theta_prop) {
+#pragma unroll
+        for (int i = 0; i < P; ++i) o.theta_prop[e * P + i] = thp[i];
+      }
+      if (o.ll_prop) o.ll_prop[e] = llp;
+      if (o.logu) o.logu[e] = logu;
+    }
+  }
+  if (tid == 0) {
+#pragma unroll
+    for (int i = 0; i < P; ++i) o.theta_end[c * P + i] = th[i];
+    o.ll_end[c] = ll;
+  }
+}
+
+struct SvArgs {
+  const VissmPmmhDesc* d;
+  uint64_t seed, row0;
+  const float* theta_cur;
+  const double* ll_cur;
+  const float *prop_chol, *prior, *h_start, *obs;
+  Out o;
+  hipStream_t st;
+};
+
+template <int N>
+void launch_sv(const SvArgs& a) {
+  hipLaunchKernelGGL((sv_pmmh_kernel<N>), dim3(a.d->C), dim3(N), 0, a.st, a.seed, a.row0, a.d->C, a.d->n_iter,
+                     a.d->it0, a.d->T_total, a.d->dt, a.theta_cur, a.ll_cur, a.prop_chol, a.prior, a.h_start, a.obs,
+                     a.o);
+}
+
 }  // namespace pmk
 }  // namespace vissm
 
@@ -310,5 +478,44 @@ extern "C" int vissm_pmmh(const VissmPmmhDesc* d, uint64_t seed, uint64_t row0, 
     default: launch_n<VISSM_MODEL_FHN>(a); break;
   }
   VISSM_CHECK_LAUNCH("pmmh");
+  return VISSM_OK;
+}
+
+extern "C" int32_t vissm_sv_pmmh_lds_bytes(int32_t N) {
+  if (!pf::valid_n(N)) return 0;
+  return 8 * N + 4 * N + 16 * (4 + 8);
+}
+
+extern "C" int vissm_sv_pmmh(const VissmPmmhDesc* d, uint64_t seed, uint64_t row0, const float* theta_cur,
+                             const double* ll_cur, const float* prop_chol, const float* prior, const float* h_start,
+                             const float* obs, float* theta_chain, double* ll_chain, int32_t* accept, float* theta_end,
+                             double* ll_end, float* theta_prop, double* ll_prop, double* logu, void* stream) {
+  // host arithmetic only, before any GPU call
+  VISSM_CHECK_ARG(d, "sv_pmmh: null descriptor");
+  VISSM_CHECK_ARG(d->model == VISSM_MODEL_SV, "sv_pmmh: model %d is not SV (vissm_pmmh has the others)", d->model);
+  VISSM_CHECK_ARG(pf::valid_n(d->N), "sv_pmmh: N=%d particles (64, 128, 256, 512 or 1024)", d->N);
+  VISSM_CHECK_ARG(d->C >= 1, "sv_pmmh: C=%d chains (at least one)", d->C);
+  VISSM_CHECK_ARG(d->n_iter >= 0 && d->it0 >= 0 && static_cast<int64_t>(d->it0) + d->n_iter < (int64_t{1} << 31),
+                  "sv_pmmh: bad iterations it0=%d n_iter=%d", d->it0, d->n_iter);
+  // (the series holds T_total + 1 values and step ta reads y[ta + 1])
+  VISSM_CHECK_ARG(d->T_total >= 0 && d->T_total < 2147483647, "sv_pmmh: T_total=%d", d->T_total);
+  // (a NaN fails the first comparison, an infinity the second)
+  VISSM_CHECK_ARG(d->dt > 0.f && d->dt <= 3.4028234e38f, "sv_pmmh: dt must be positive and finite, got %g",
+                  static_cast<double>(d->dt));
+  VISSM_CHECK_ARG(theta_cur && ll_cur && prop_chol && prior && h_start && theta_end && ll_end,
+                  "sv_pmmh: null pointer");
+  VISSM_CHECK_ARG(d->n_iter == 0 || (theta_chain && ll_chain && accept), "sv_pmmh: null pointer (n_iter > 0)");
+  VISSM_CHECK_ARG(d->T_total == 0 || obs, "sv_pmmh: null pointer (T_total > 0)");
+  const SvArgs a{d,   seed, row0, theta_cur, ll_cur, prop_chol, prior, h_start,
+                 obs, Out{theta_chain, ll_chain, accept, theta_end, ll_end, theta_prop, ll_prop, logu},
+                 as_stream(stream)};
+  switch (d->N) {
+    case 64: launch_sv<64>(a); break;
+    case 128: launch_sv<128>(a); break;
+    case 256: launch_sv<256>(a); break;
+    case 512: launch_sv<512>(a); break;
+    default: launch_sv<1024>(a); break;
+  }
+  VISSM_CHECK_LAUNCH("sv_pmmh");
   return VISSM_OK;
 }

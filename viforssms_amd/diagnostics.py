@@ -26,7 +26,8 @@ SMOOTH_SEED_XOR = 0x5300714E
 # proposals and uniforms): a sixth key
 MCMC_SEED_XOR = 0x3C3C7E7A
 # filter steps one block runs per launch of theta_mcmc(): a launch holds max(1, MCMC_LAUNCH_STEPS // T) iterations.
-# Measured at N = 1024 and 64 chains: 3.1 us per AR step, 0.81 s per launch at T = 5000
+# Measured at N = 1024 and 64 chains: 3.1 us per AR step, 0.81 s per launch at T = 5000;
+# volatility_mcmc() (section 4.13): 4.3 us per SV step, 1.12 s per launch at T = 1508
 MCMC_LAUNCH_STEPS = 1 << 18
 # device bytes of the filter's cloud [K N, S, T] fp32 that particle_smoother() may keep for its backward pass
 SMOOTH_CLOUD_BYTES = 8 << 30
@@ -303,21 +304,12 @@ class PosteriorDiagnostics:
         mcmc/{mean, sd} [P] and mcmc/quantiles [Q, P] summarise the pooled draws on theta/quantiles' scale
         (log-parameters exponentiated) at the same probs and by the same estimator, with theta/{mean, sd, quantiles}
         of q(theta) copied in beside them; mcmc/rhat [P] is the split-R-hat of the raw draws; mcmc/prop_chol [P, P].
-        SV has no observation model: ValueError."""
+        SV has no observation model: ValueError (volatility_mcmc() is SV's)."""
         from . import ops
         md = self.mdef
         if md.model_id == _lib.MODEL_SV or getattr(self, "filter_data", None) is None:
             raise ValueError("theta_mcmc: SV has no observation model (its first coordinate is the observed series)")
-        C, N, n_iter, burn = int(n_chains), int(n_particles), int(n_iter), int(burn_in)
-        if N not in _lib.PF_PARTICLES:
-            raise ValueError(f"theta_mcmc: n_particles={N}, one of {_lib.PF_PARTICLES} expected")
-        if not 1 <= C <= self.p_local:
-            raise ValueError(f"theta_mcmc: n_chains={C} outside 1 .. p_local = {self.p_local}")
-        if not 0 <= burn < n_iter:
-            raise ValueError(f"theta_mcmc: burn_in={burn} outside 0 .. n_iter - 1 = {n_iter - 1}")
-        if not 0.0 < float(step_scale) < float("inf"):
-            raise ValueError(f"theta_mcmc: step_scale={step_scale} must be positive and finite")
-        p = _check_probs(probs)
+        C, N, n_iter, burn, p = self._mcmc_args("theta_mcmc", n_chains, n_particles, n_iter, burn_in, step_scale, probs)
         dev = self.engine.device
         P = _lib.MODEL_P[md.model_id]
         obs_h, bin_h, x0_h = self.filter_data
@@ -325,6 +317,39 @@ class PosteriorDiagnostics:
         obs = torch.as_tensor(np.ascontiguousarray(obs_h[:, :T]), device=dev)
         obs_bin = torch.as_tensor(np.ascontiguousarray(bin_h[:, :T]), device=dev)
         x0 = torch.as_tensor(np.asarray(x0_h, dtype=np.float32).reshape(-1), device=dev)
+        draw, chol, L, prior = self._mcmc_walk("theta_mcmc", P, step_scale)
+        seed = self.engine.seed ^ MCMC_SEED_XOR
+        row0 = self.global_step * C * N * (n_iter + 1)
+        th = draw[:C].contiguous()
+        ll = ops.particle_filter(md.model_id, th, x0, obs, obs_bin, md.dt, md.obs_std, N, seed, row0, cloud=False,
+                                 proposal="adapted").loglik
+        per = max(1, MCMC_LAUNCH_STEPS // max(T, 1))
+        runs = []
+        for it0 in range(0, n_iter, per):
+            r = ops.pmmh(md.model_id, th, ll, L, prior, x0, obs, obs_bin, md.dt, md.obs_std, N,
+                         min(per, n_iter - it0), seed, row0 + C * N, it0=it0)
+            th, ll = r.theta_end, r.ll_end
+            runs.append(r)
+        return self._mcmc_result(runs, burn, p, probs, chol, draw)
+
+    def _mcmc_args(self, what, n_chains, n_particles, n_iter, burn_in, step_scale, probs):
+        """The checks theta_mcmc() and volatility_mcmc() share: (C, N, n_iter, burn, p)."""
+        C, N, n_iter, burn = int(n_chains), int(n_particles), int(n_iter), int(burn_in)
+        if N not in _lib.PF_PARTICLES:
+            raise ValueError(f"{what}: n_particles={N}, one of {_lib.PF_PARTICLES} expected")
+        if not 1 <= C <= self.p_local:
+            raise ValueError(f"{what}: n_chains={C} outside 1 .. p_local = {self.p_local}")
+        if not 0 <= burn < n_iter:
+            raise ValueError(f"{what}: burn_in={burn} outside 0 .. n_iter - 1 = {n_iter - 1}")
+        if not 0.0 < float(step_scale) < float("inf"):
+            raise ValueError(f"{what}: step_scale={step_scale} must be positive and finite")
+        return C, N, n_iter, burn, _check_probs(probs)
+
+    def _mcmc_walk(self, what, P, step_scale):
+        """The raw theta draw posterior_summary uses (rank 0's rows, broadcast), the factor of the random walk's
+        covariance step_scale^2 (2.38^2 / P) Sigma_q in float64 and as the fp32 device tensor the kernel takes, and
+        the model's prior [P, 2]: (draw, chol, L, prior)."""
+        dev = self.engine.device
         _, theta = self.sample_paths_theta(np.tile(0, self.p_local), step=self.global_step)
         draw = theta.detach().float().contiguous()
         if self.dist.world > 1:
@@ -337,27 +362,20 @@ class PosteriorDiagnostics:
                 raise np.linalg.LinAlgError
             chol = np.linalg.cholesky(float(step_scale) ** 2 * (2.38 ** 2 / P) * sigma)
         except np.linalg.LinAlgError:
-            raise ValueError("theta_mcmc: the sample covariance of q(theta) is not positive definite") from None
+            raise ValueError(f"{what}: the sample covariance of q(theta) is not positive definite") from None
         L = torch.as_tensor(chol.astype(np.float32), device=dev)
-        prior = torch.as_tensor(np.asarray(md.priors, dtype=np.float32).reshape(P, 2), device=dev)
-        seed = self.engine.seed ^ MCMC_SEED_XOR
-        row0 = self.global_step * C * N * (n_iter + 1)
-        th = draw[:C].contiguous()
-        ll = ops.particle_filter(md.model_id, th, x0, obs, obs_bin, md.dt, md.obs_std, N, seed, row0, cloud=False,
-                                 proposal="adapted").loglik
-        per = max(1, MCMC_LAUNCH_STEPS // max(T, 1))
-        chains, lls, accs = [], [], []
-        for it0 in range(0, n_iter, per):
-            r = ops.pmmh(md.model_id, th, ll, L, prior, x0, obs, obs_bin, md.dt, md.obs_std, N,
-                         min(per, n_iter - it0), seed, row0 + C * N, it0=it0)
-            th, ll = r.theta_end, r.ll_end
-            chains.append(r.theta_chain)
-            lls.append(r.ll_chain)
-            accs.append(r.accept)
-        kept = torch.cat(chains, 1)[:, burn:].contiguous()
+        prior = torch.as_tensor(np.asarray(self.mdef.priors, dtype=np.float32).reshape(P, 2), device=dev)
+        return draw, chol, L, prior
+
+    def _mcmc_result(self, runs, burn, p, probs, chol, draw) -> Dict[str, np.ndarray]:
+        """The result of theta_mcmc() / volatility_mcmc() from the chained launches' PmmhResults."""
+        md, dev = self.mdef, self.engine.device
+        P = _lib.MODEL_P[md.model_id]
+        kept = torch.cat([r.theta_chain for r in runs], 1)[:, burn:].contiguous()
         res: Dict[str, np.ndarray] = {"probs": p, "mcmc/theta": kept.cpu().numpy(),
-                                      "mcmc/loglik": torch.cat(lls, 1)[:, burn:].cpu().numpy(),
-                                      "mcmc/accept_rate": torch.cat(accs, 1)[:, burn:].double().mean(1).cpu().numpy(),
+                                      "mcmc/loglik": torch.cat([r.ll_chain for r in runs], 1)[:, burn:].cpu().numpy(),
+                                      "mcmc/accept_rate": torch.cat([r.accept for r in runs], 1)[:, burn:].double()
+                                      .mean(1).cpu().numpy(),
                                       "mcmc/prop_chol": chol}
         pooled = kept.view(-1, P)
         pos = list(md.theta_pos)
@@ -379,6 +397,47 @@ class PosteriorDiagnostics:
                         burn_in: int = 500, step_scale: float = 1.0, probs=DEFAULT_PROBS) -> Dict[str, np.ndarray]:
         """theta_mcmc written as one .npz by rank 0 (every rank computes the same result)."""
         return self._save_npz(PATH, self.theta_mcmc(n_chains, n_particles, n_iter, burn_in, step_scale, probs))
+
+    # ------------------------------------------------------------------ the theta posterior of the SV family
+    @torch.no_grad()
+    def volatility_mcmc(self, n_chains: int = 64, n_particles: int = 256, n_iter: int = 2000, burn_in: int = 500,
+                        step_scale: float = 1.0, probs=DEFAULT_PROBS) -> Dict[str, np.ndarray]:
+        """theta_mcmc() for the SV family, which theta_mcmc() refuses: the same chains (ops.sv_pmmh) around
+        volatility_filter()'s filter, which is exactly fully adapted.  The data and its refusals are that method's: the
+        observed series y[0 .. T], every particle started at x0; ValueError for a family other than SV, a y[0 .. T]
+        that is not finite, a y[0 .. T - 1] equal to 0.  The prior, the random walk's covariance step_scale^2 (2.38^2 /
+        4) Sigma_q, the start at samples 0 .. C - 1 of the broadcast draw, the Philox key seed ^ MCMC_SEED_XOR, the rows
+        based at global_step C N (n_iter + 1) (the initial estimates, ops.sv_filter(cloud=False), take the first C N),
+        the launches of max(1, MCMC_LAUNCH_STEPS // T) iterations and every returned key are theta_mcmc()'s."""
+        from . import ops
+        md = self.mdef
+        if md.model_id != _lib.MODEL_SV:
+            raise ValueError(f"volatility_mcmc: the {md.family} family has an observation model: theta_mcmc() is its "
+                             "check; this one is SV's")
+        C, N, n_iter, burn, p = self._mcmc_args("volatility_mcmc", n_chains, n_particles, n_iter, burn_in, step_scale,
+                                                probs)
+        y_h, T = self._volatility_series("volatility_mcmc")
+        dev = self.engine.device
+        P = _lib.MODEL_P[md.model_id]
+        obs = torch.as_tensor(y_h, device=dev)
+        h0 = torch.full((1,), float(self.x0), dtype=torch.float32, device=dev)
+        draw, chol, L, prior = self._mcmc_walk("volatility_mcmc", P, step_scale)
+        seed = self.engine.seed ^ MCMC_SEED_XOR
+        row0 = self.global_step * C * N * (n_iter + 1)
+        th = draw[:C].contiguous()
+        ll = ops.sv_filter(th, h0, obs, md.dt, N, seed, row0, cloud=False).loglik
+        per = max(1, MCMC_LAUNCH_STEPS // max(T, 1))
+        runs = []
+        for it0 in range(0, n_iter, per):
+            r = ops.sv_pmmh(th, ll, L, prior, h0, obs, md.dt, N, min(per, n_iter - it0), seed, row0 + C * N, it0=it0)
+            th, ll = r.theta_end, r.ll_end
+            runs.append(r)
+        return self._mcmc_result(runs, burn, p, probs, chol, draw)
+
+    def save_volatility_mcmc(self, PATH: str, n_chains: int = 64, n_particles: int = 256, n_iter: int = 2000,
+                             burn_in: int = 500, step_scale: float = 1.0, probs=DEFAULT_PROBS) -> Dict[str, np.ndarray]:
+        """volatility_mcmc written as one .npz by rank 0 (every rank computes the same result)."""
+        return self._save_npz(PATH, self.volatility_mcmc(n_chains, n_particles, n_iter, burn_in, step_scale, probs))
 
     # ------------------------------------------------------------------ particle smoother
     @torch.no_grad()
@@ -461,14 +520,7 @@ class PosteriorDiagnostics:
         chunk = self.filter_chunk(K, N) if chunk is None else int(chunk)
         if chunk < 1:
             raise ValueError(f"{what} chunk {chunk} < 1")
-        y_h = np.asarray(self.obs, dtype=np.float32).reshape(-1)
-        T = min(int(self.target_len()), y_h.shape[0] - 1)
-        y_h = np.ascontiguousarray(y_h[:T + 1])
-        if not np.isfinite(y_h).all():
-            raise ValueError(f"{what}: the observed series y[0 .. {T}] is not finite")
-        if np.any(y_h[:T] == 0.0):
-            raise ValueError(f"{what}: y[{int(np.flatnonzero(y_h[:T] == 0.0)[0])}] = 0: the density of the next "
-                             "observation degenerates there")
+        y_h, T = self._volatility_series(what)
         if keep is not None:
             M, cap = keep
             if not (_lib.PS_MIN_PATHS <= M <= N and M & (M - 1) == 0):
@@ -508,6 +560,19 @@ class PosteriorDiagnostics:
         res["filter/ess"] = torch.cat(esss + [torch.zeros(K, 0, device=dev)], 1).cpu().numpy()
         res.update(stack_bands("filter", parts, 1, Q))
         return res, th, obs, clouds
+
+    def _volatility_series(self, what):
+        """The observed series y[0 .. T] fp32 the SV filter reads and T, refused where it is not finite or a y[0 .. T - 1]
+        is 0."""
+        y_h = np.asarray(self.obs, dtype=np.float32).reshape(-1)
+        T = min(int(self.target_len()), y_h.shape[0] - 1)
+        y_h = np.ascontiguousarray(y_h[:T + 1])
+        if not np.isfinite(y_h).all():
+            raise ValueError(f"{what}: the observed series y[0 .. {T}] is not finite")
+        if np.any(y_h[:T] == 0.0):
+            raise ValueError(f"{what}: y[{int(np.flatnonzero(y_h[:T] == 0.0)[0])}] = 0: the density of the next "
+                             "observation degenerates there")
+        return y_h, T
 
     def save_volatility_filter(self, PATH: str, n_theta: int = 64, n_particles: int = 1024, probs=DEFAULT_PROBS,
                                chunk: Optional[int] = None) -> Dict[str, np.ndarray]:

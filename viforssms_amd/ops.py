@@ -1330,3 +1330,63 @@ def pmmh(model_id: int, theta_cur: torch.Tensor, ll_cur: torch.Tensor, prop_chol
                                  ptr(theta_end), ptr(ll_end), ptr(tp), ptr(lpr), ptr(lu), _lib.stream_handle(dev)),
           "vissm_pmmh")
     return PmmhResult(theta_chain, ll_chain, accept, theta_end, ll_end, tp, lpr, lu)
+
+
+def sv_pmmh(theta_cur: torch.Tensor, ll_cur: torch.Tensor, prop_chol: torch.Tensor, prior: torch.Tensor,
+            h_start: torch.Tensor, obs: torch.Tensor, dt: float, N: int, n_iter: int, seed: int, row0: int,
+            it0: int = 0, trace: bool = False) -> PmmhResult:
+    """pmmh for the stochastic-volatility model, which pmmh refuses: n_iter iterations of C chains, one per row of
+    theta_cur [C, 4] (raw); vissm_sv_pmmh: one block per chain, the whole chain in one launch.  An iteration proposes
+    theta' = theta + L xi with prop_chol = L [4, 4] (lower), estimates log p(y | theta') with sv_filter's filter of N
+    particles (exactly fully adapted) over the series obs = y[0 .. T] (T + 1 values), every particle started at
+    h_start [1], and accepts iff log u < (ll' - ll) + (lp' - lp), lp the independent Gaussian log-prior of
+    prior [4, 2] = (mean, sd).  ll_cur [C] float64 is the estimate that goes with theta_cur:
+    sv_filter(cloud=False).loglik.  Iteration i of chain c uses the Philox rows row0 + (i C + c) N .. + N - 1: its
+    filter is sv_filter's for K = C at row0 + i C N, its proposal and uniform sit on counter word 1 = 2 of the first of
+    them.  A call with it0' = it0 + n_iter, theta_cur = theta_end and ll_cur = ll_end continues bitwise.  trace: also
+    the proposals, their estimates and log u."""
+    # the refusals of the C entry, by host arithmetic before any GPU call
+    P = _lib.MODEL_P[_lib.MODEL_SV]
+    N, n_iter, it0 = int(N), int(n_iter), int(it0)
+    if N not in _lib.PF_PARTICLES:
+        raise ValueError(f"sv_pmmh: N={N} particles, one of {_lib.PF_PARTICLES} expected")
+    if not 0.0 < float(dt) < float("inf"):
+        raise ValueError(f"sv_pmmh: dt must be positive and finite, got {dt}")
+    if theta_cur.dim() != 2 or theta_cur.shape[1] != P or theta_cur.shape[0] < 1:
+        raise ValueError(f"sv_pmmh: theta_cur [C >= 1, {P}] expected, got {tuple(theta_cur.shape)}")
+    C = theta_cur.shape[0]
+    if n_iter < 0 or it0 < 0 or it0 + n_iter >= 2 ** 31:
+        raise ValueError(f"sv_pmmh: bad iterations it0={it0} n_iter={n_iter}")
+    if obs.dim() != 1 or obs.shape[0] < 1 or obs.dtype != torch.float32:
+        raise ValueError(f"sv_pmmh: obs: an fp32 vector y[0 .. T] expected, got {obs.dtype} {tuple(obs.shape)}")
+    T_total = obs.shape[0] - 1
+    if T_total >= 2 ** 31 - 1:
+        raise ValueError(f"sv_pmmh: T = {T_total} reaches 2^31 - 1")
+    if not 0 <= int(row0) < 2 ** 64:
+        raise ValueError(f"sv_pmmh: row0={row0} outside [0, 2^64)")
+    _require_gpu(theta_cur, prop_chol, prior, h_start, obs)
+    for name, t, shape in (("theta_cur", theta_cur, (C, P)), ("prop_chol", prop_chol, (P, P)),
+                           ("prior", prior, (P, 2)), ("h_start", h_start, (1,))):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape:
+            raise ValueError(f"sv_pmmh: fp32 {name} {list(shape)} expected, got {t.dtype} {tuple(t.shape)}")
+    dev = theta_cur.device
+    if not ll_cur.is_cuda or ll_cur.dtype != torch.float64 or tuple(ll_cur.shape) != (C,) or \
+            not ll_cur.is_contiguous():
+        raise ValueError(f"sv_pmmh: ll_cur: a contiguous float64 GPU tensor [{C}] expected")
+    if any(t.device != dev for t in (ll_cur, prop_chol, prior, h_start, obs)):
+        raise ValueError("sv_pmmh: all tensors on one device expected")
+    key, row = ctypes.c_uint64(seed & (2 ** 64 - 1)), ctypes.c_uint64(int(row0))
+    theta_chain = torch.empty(C, n_iter, P, dtype=torch.float32, device=dev)
+    ll_chain = torch.empty(C, n_iter, dtype=torch.float64, device=dev)
+    accept = torch.empty(C, n_iter, dtype=torch.int32, device=dev)
+    theta_end = torch.empty(C, P, dtype=torch.float32, device=dev)
+    ll_end = torch.empty(C, dtype=torch.float64, device=dev)
+    tp = torch.empty(C, n_iter, P, dtype=torch.float32, device=dev) if trace else None
+    lpr = torch.empty(C, n_iter, dtype=torch.float64, device=dev) if trace else None
+    lu = torch.empty(C, n_iter, dtype=torch.float64, device=dev) if trace else None
+    d = _lib.PmmhDesc(_lib.MODEL_SV, C, N, n_iter, it0, T_total, float(dt), 0.0)
+    check(_lib.load().vissm_sv_pmmh(ctypes.byref(d), key, row, ptr(theta_cur), ptr(ll_cur), ptr(prop_chol), ptr(prior),
+                                    ptr(h_start), ptr(obs), ptr(theta_chain), ptr(ll_chain), ptr(accept),
+                                    ptr(theta_end), ptr(ll_end), ptr(tp), ptr(lpr), ptr(lu), _lib.stream_handle(dev)),
+          "vissm_sv_pmmh")
+    return PmmhResult(theta_chain, ll_chain, accept, theta_end, ll_end, tp, lpr, lu)

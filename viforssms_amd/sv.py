@@ -75,14 +75,21 @@ def run(argv=None):
                     help="After training, run the K filters of --filter, draw M smoothing trajectories per filter by "
                          "backward simulation (M a power of two, 64 <= M <= N) and write the filter's entries and "
                          "the smoothing bands to this .npz file")
+    ap.add_argument("--mcmc", nargs=4, metavar=("C", "N", "ITER", "PATH"), default=None,
+                    help="After training, run C particle marginal Metropolis-Hastings chains of ITER iterations on the "
+                         "GPU, each around a particle filter of the log-volatility with N particles (64 .. 1024, a power "
+                         "of two), started at posterior theta samples, and write the draws of p(theta | y) after a "
+                         "burn-in of ITER / 4, their quantiles beside q(theta)'s and the split-R-hat to this .npz file")
     args = ap.parse_args(argv)
-    for name, n_int in (("filter", 2), ("smooth", 3)):
+    for name, n_int in (("filter", 2), ("smooth", 3), ("mcmc", 3)):
         v = getattr(args, name)
         if v is not None:
             try:
                 setattr(args, name, tuple(int(a) for a in v[:n_int]) + (v[n_int],))
             except ValueError:
                 ap.error(f"--{name}: integers expected, got {v[:n_int]!r}")
+    if args.mcmc is not None and (args.mcmc[0] < 1 or args.mcmc[1] not in _lib.PF_PARTICLES or args.mcmc[2] < 2):
+        ap.error("--mcmc: C >= 1, N one of 64, 128, 256, 512, 1024 and ITER >= 2 expected")
     np.random.seed(1)
     ctx = init_distributed()
     obs = load_sv()
@@ -103,4 +110,7 @@ def run(argv=None):
         model.save_volatility_filter(args.filter[2], args.filter[0], args.filter[1])
     if args.smooth:
         model.save_volatility_smoother(args.smooth[3], args.smooth[0], args.smooth[1], args.smooth[2])
+    if args.mcmc:
+        # a quarter of the iterations is burn-in, as the default's
+        model.save_volatility_mcmc(args.mcmc[3], args.mcmc[0], args.mcmc[1], args.mcmc[2], burn_in=args.mcmc[2] // 4)
     return model
