@@ -359,6 +359,12 @@ typedef struct {
 } VissmFeatGrads;
 
 size_t vissm_feat_workspace_size(const VissmFeatDesc* d);
+/* The launch geometry vissm_feat_fwd (backward = 0) / vissm_feat_bwd (backward != 0) pick for d now (host-side
+ * arithmetic, no GPU call; the VISSM_FEAT_KT / VISSM_FEAT_KT_BWD overrides included): out[0] = output positions per
+ * block (8, 16 or 32: the kernel instantiation), out[1] = blocks per window, out[2] = dynamic LDS bytes of the
+ * launch.  VISSM_EINVAL for a descriptor the kernels refuse.  No reference equivalent (TF1 has no launch geometry):
+ * the tests assert through it which variant they ran. */
+int vissm_feat_geometry(const VissmFeatDesc* d, int32_t backward, int32_t* out);
 int vissm_feat_fwd(const VissmFeatDesc* d, const VissmFeatParams* w, const float* h0, float* C, float* act,
                    void* stream);
 int vissm_feat_bwd(const VissmFeatDesc* d, const VissmFeatParams* w, const float* h0, const float* act,

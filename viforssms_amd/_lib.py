@@ -159,6 +159,7 @@ SIGNATURES = {
                                         _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                                         ctypes.POINTER(FlowGrads), _c_void_p, _size_t, _c_void_p]),
     "vissm_feat_workspace_size": (_size_t, [ctypes.POINTER(FeatDesc)]),
+    "vissm_feat_geometry": (_i32, [ctypes.POINTER(FeatDesc), _i32, ctypes.POINTER(_i32)]),
     "vissm_feat_fwd": (_i32, [ctypes.POINTER(FeatDesc), ctypes.POINTER(FeatParams), _c_void_p, _c_void_p, _c_void_p,
                               _c_void_p]),
     "vissm_feat_bwd": (_i32, [ctypes.POINTER(FeatDesc), ctypes.POINTER(FeatParams), _c_void_p, _c_void_p, _c_void_p,
@@ -290,6 +291,14 @@ def flow_geometry(desc: FlowDesc, which: int) -> dict:
     out = (_i32 * 4)()
     check(load().vissm_flow_geometry(ctypes.byref(desc), which, out), "vissm_flow_geometry")
     return {"tile": out[0], "chunk_tiles": out[1], "n_chunks": out[2], "n_groups": out[3]}
+
+
+def feat_geometry(desc: FeatDesc, backward: bool) -> dict:
+    """vissm_feat_geometry: the variant vissm_feat_fwd / vissm_feat_bwd launch for `desc` now (the VISSM_FEAT_KT /
+    VISSM_FEAT_KT_BWD overrides included).  Host arithmetic only, callable without a GPU."""
+    out = (_i32 * 3)()
+    check(load().vissm_feat_geometry(ctypes.byref(desc), int(bool(backward)), out), "vissm_feat_geometry")
+    return {"kt": out[0], "blocks": out[1], "lds_bytes": out[2]}
 
 
 def ptr(t) -> Optional[int]:

@@ -696,6 +696,19 @@ size_t vissm_feat_workspace_size(const VissmFeatDesc* d) {
   return align_up(static_cast<size_t>(a.n_win) * nb * of.n * sizeof(float)) + align_up(of.n * sizeof(float));
 }
 
+int vissm_feat_geometry(const VissmFeatDesc* d, int32_t backward, int32_t* out) {
+  feat::Args a;
+  int rc = feat::make(d, &a);
+  if (rc) return rc;
+  VISSM_CHECK_ARG(out, "feat_geometry: null pointer");
+  const bool bwd = backward != 0;
+  const int kt = feat::pick_kt(a, bwd);
+  out[0] = kt;
+  out[1] = bwd ? feat::bwd_blocks(a, kt) : (a.Lh + kt - 1) / kt;
+  out[2] = static_cast<int32_t>(bwd ? feat::bwd_smem(a, kt) : feat::fwd_smem(a, kt));
+  return VISSM_OK;
+}
+
 int vissm_feat_fwd(const VissmFeatDesc* d, const VissmFeatParams* w, const float* h0, float* C, float* act,
                    void* stream) {
   feat::Args a;

@@ -335,9 +335,10 @@ class LvFeatConvFn(torch.autograd.Function):
         ws = (W0, b0, W1, b1, W2, b2, W3, b3, conv_w, conv_b)
         _require_gpu(*ws)
         n_win, R, Cin = h0.shape
-        if h0.dtype != torch.float32 or h0.stride(2) != 1 or h0.stride(1) != Cin:
+        # windows may lie further apart than R Cin (a view whose rows are contiguous: in_win_stride below)
+        if not h0.is_cuda or h0.dtype != torch.float32 or h0.stride(2) != 1 or h0.stride(1) != Cin:
             h0 = h0.contiguous()
-        _require_gpu(h0)
+            _require_gpu(h0)
         H, U, k = W0.shape[1], W3.shape[1], conv_w.shape[0]
         if tuple(conv_w.shape) != (k, 1 + R, H) or s * (Lh - 1) + k > U or H >= 64:
             raise _lib.VissmError(f"lv_feat: conv_w {tuple(conv_w.shape)}, R {R}, U {U}, Lh {Lh}, s {s}: shapes "
@@ -426,9 +427,10 @@ class SvFeatConvFn(torch.autograd.Function):
         ws = (W0, b0, W1, b1, W2, b2, W3, b3, conv_w, conv_b)
         _require_gpu(*ws)
         n_win, L, Cr = ts.shape
-        if ts.dtype != torch.float32 or ts.stride(2) != 1 or ts.stride(1) != Cr:
+        # windows may lie further apart than L Cr (a view whose rows are contiguous: in_win_stride below)
+        if not ts.is_cuda or ts.dtype != torch.float32 or ts.stride(2) != 1 or ts.stride(1) != Cr:
             ts = ts.contiguous()
-        _require_gpu(ts)
+            _require_gpu(ts)
         R, Cin = L - 1, 2 * Cr - 2
         H, k = W0.shape[1], conv_w.shape[0]
         if (tuple(W0.shape) != (Cin, H) or tuple(W3.shape) != (H, H) or tuple(conv_w.shape) != (k, 1 + H, H)
