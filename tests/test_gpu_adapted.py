@@ -98,7 +98,10 @@ def test_without_observations_it_is_the_bootstrap_filter(model, K, N, H):
     (SU.AR, "all", 3, 64, 65), (SU.AR, "tenth", 1, 1024, 131), (SU.AR, "all", 3, 128, 1),
     (SU.LV, "all", 3, 128, 64), (SU.LV, "first", 3, 64, 63), (SU.LV, "second", 1, 1024, 65),
     (SU.LV, "tenth", 1, 128, 131), (SU.FHN, "all", 1, 128, 131), (SU.FHN, "second", 3, 64, 65),
-    (SU.FHN, "first", 3, 1024, 63), (SU.FHN, "all", 3, 1024, 1)])
+    (SU.FHN, "first", 3, 1024, 63), (SU.FHN, "all", 3, 1024, 1),
+    # four and eight waves (two and four trips of the partial-sum loop), one tile boundary each
+    (SU.AR, "tenth", 3, 256, 65), (SU.AR, "first", 3, 512, 65), (SU.LV, "second", 3, 256, 65),
+    (SU.LV, "first", 3, 512, 33), (SU.FHN, "tenth", 3, 256, 65), (SU.FHN, "second", 3, 512, 33)])
 def test_teacher_forced_parity(model, pattern, K, N, H):
     """Step t of the reference starts from the kernel's own cloud at t - 1 (x_start at t = 0).  At an observed step
     the weights are those of that *pre-step* cloud: the kernel's logw_i and m each lie within d = 8 * max(e32, 2^-20

@@ -84,7 +84,10 @@ def test_without_observations_the_cloud_is_the_forecast(model, K, N, H):
     (SU.AR, "all", 3, 64, 65), (SU.AR, "tenth", 1, 1024, 131), (SU.AR, "all", 5, 128, 1),
     (SU.LV, "all", 3, 128, 64), (SU.LV, "coord", 5, 64, 63), (SU.LV, "tenth", 1, 1024, 65),
     (SU.FHN, "all", 1, 128, 131), (SU.FHN, "coord", 3, 64, 65), (SU.FHN, "tenth", 3, 1024, 63),
-    (SU.FHN, "all", 5, 1024, 1)])
+    (SU.FHN, "all", 5, 1024, 1),
+    # four and eight waves (two and four trips of the partial-sum loop), one tile boundary each
+    (SU.AR, "tenth", 3, 256, 65), (SU.AR, "coord", 3, 512, 65), (SU.LV, "coord", 3, 256, 65),
+    (SU.LV, "coord", 3, 512, 33), (SU.FHN, "tenth", 3, 256, 65), (SU.FHN, "coord", 3, 512, 33)])
 def test_teacher_forced_parity(model, pattern, K, N, H):
     """Step t of the reference starts from the kernel's own cloud at t - 1, so rounding does not compound and a
     resampling decision of the kernel is never second-guessed: given its traced weights its ancestors must be the

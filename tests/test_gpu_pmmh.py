@@ -75,7 +75,9 @@ def _ulps32(a, b):
 REPLAY = [(SU.AR, 3, 64, 65, 5, "all"), (SU.AR, 1, 1024, 63, 5, "tenth"), (SU.AR, 3, 128, 1, 1, "all"),
           (SU.LV, 3, 128, 65, 5, "all"), (SU.LV, 1, 64, 63, 5, "coord"), (SU.LV, 3, 1024, 65, 1, "tenth"),
           (SU.LV, 1, 128, 1, 5, "tenth"), (SU.FHN, 3, 64, 63, 5, "all"), (SU.FHN, 1, 1024, 65, 5, "coord"),
-          (SU.FHN, 3, 128, 63, 1, "tenth"), (SU.FHN, 3, 1024, 1, 5, "all")]
+          (SU.FHN, 3, 128, 63, 1, "tenth"), (SU.FHN, 3, 1024, 1, 5, "all"),
+          # four and eight waves: two and four trips of the partial-sum loop
+          (SU.AR, 3, 256, 65, 5, "tenth"), (SU.LV, 3, 512, 65, 5, "coord"), (SU.FHN, 3, 256, 65, 5, "coord")]
 
 
 @pytest.mark.parametrize("model,C,N,T,n_iter,pattern", REPLAY)

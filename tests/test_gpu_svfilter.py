@@ -80,7 +80,8 @@ def _q_tol(qref, lw64, lw32, m64, live):
 # ----------------------------------------------------------------------------------------------------------------
 # 1. teacher-forced parity
 # ----------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("K,N,H", [(3, 64, 65), (1, 1024, 131), (3, 128, 1), (1, 128, 63), (3, 1024, 64)])
+@pytest.mark.parametrize("K,N,H", [(3, 64, 65), (1, 1024, 131), (3, 128, 1), (1, 128, 63), (3, 1024, 64),
+                                     (3, 256, 65), (1, 512, 65)])
 def test_teacher_forced_parity(K, N, H):
     from viforssms_amd import ops
     rng = np.random.default_rng(10 * N + H + K)

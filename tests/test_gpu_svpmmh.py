@@ -67,6 +67,8 @@ def _ulps32(a, b):
 
 
 REPLAY = list(itertools.product((64, 128, 1024), (1, 3), (1, 5), (1, 4, 5, 63, 65)))
+# four and eight waves: two and four trips of the partial-sum loop
+REPLAY += list(itertools.product((256, 512), (1, 3), (1, 5), (5, 65)))
 
 
 @pytest.mark.parametrize("N,C,n_iter,T", REPLAY)

@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <string>
 #include <cstdio>
+#include <type_traits>
 
 #include "../../include/vissm.h"
 #include "rng_math.hpp"
@@ -33,6 +34,28 @@ void set_error(const char* fmt, ...);
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 static inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
+
+// The particle kernels are templates on the particle count N (64, 128, 256, 512 or 1024: pf::valid_n, checked by the
+// caller) and on the model (AR, LV or FHN, checked by the caller): f gets the value as a std::integral_constant.
+template <class F>
+void dispatch_n(int N, F&& f) {
+  switch (N) {
+    case 64: f(std::integral_constant<int, 64>{}); break;
+    case 128: f(std::integral_constant<int, 128>{}); break;
+    case 256: f(std::integral_constant<int, 256>{}); break;
+    case 512: f(std::integral_constant<int, 512>{}); break;
+    default: f(std::integral_constant<int, 1024>{}); break;
+  }
+}
+
+template <class F>
+void dispatch_model(int model, F&& f) {
+  switch (model) {
+    case VISSM_MODEL_AR: f(std::integral_constant<int, VISSM_MODEL_AR>{}); break;
+    case VISSM_MODEL_LV: f(std::integral_constant<int, VISSM_MODEL_LV>{}); break;
+    default: f(std::integral_constant<int, VISSM_MODEL_FHN>{}); break;
+  }
+}
 
 // ---------------------------------------------------------------------------
 // Philox4x32-10 and u01 (rng_math.hpp, shared with the host checks); Box-Muller on the 4 outputs gives
@@ -74,6 +97,23 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+  return v;
+}
+
+// inclusive scan over the wave's 64 lanes
+__device__ __forceinline__ uint64_t wave_scan(uint64_t v, int lane) {
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const uint32_t lo = __shfl_up(static_cast<uint32_t>(v), off, 64);
+    const uint32_t hi = __shfl_up(static_cast<uint32_t>(v >> 32), off, 64);
+    if (lane >= off) v += (static_cast<uint64_t>(hi) << 32) | lo;
+  }
+  return v;
+}
+
 // Fixed-order block sum; all threads get the result.  `red` must hold blockDim/64 entries.
 template <typename T>
 __device__ __forceinline__ T block_sum(T v, T* red) {
@@ -97,6 +137,10 @@ __device__ __forceinline__ float softplus_f(float x) {
 __device__ __forceinline__ float sigmoid_f(float x) {
   return x >= 0.f ? 1.f / (1.f + expf(-x)) : expf(x) / (1.f + expf(x));
 }
+
+// the checks vissm_particle_filter(_adapted) and vissm_sv_filter share (particle.hip): N, the shape, K N and the
+// null pointers, with the entry's name in the message; VISSM_OK or VISSM_EINVAL
+int check_filter_args(const char* name, const VissmPfDesc* d, bool pointers, bool pointers_h);
 
 constexpr float kLog2Pi = 1.8378770664093453f;
 constexpr float kBnScale = 0.99950037468777f;  // 1/sqrt(1 + 1e-3)

@@ -49,23 +49,6 @@ constexpr int tile_depth(int S, int N) {
   return d > 64 ? 64 : d;
 }
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
-}
-
-// inclusive scan over the wave's 64 lanes
-__device__ __forceinline__ uint64_t wave_scan(uint64_t v, int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t lo = __shfl_up(static_cast<uint32_t>(v), off, 64);
-    const uint32_t hi = __shfl_up(static_cast<uint32_t>(v >> 32), off, 64);
-    if (lane >= off) v += (static_cast<uint64_t>(hi) << 32) | lo;
-  }
-  return v;
-}
-
 template <int MODEL, int N, int PROPOSAL>
 __global__ __launch_bounds__(N) void particle_filter_kernel(
     uint64_t seed, uint64_t row0, int H, int t0, int T_total, float dt, float obs_std, const float* __restrict__ theta,
@@ -241,45 +224,19 @@ __global__ __launch_bounds__(N) void particle_filter_kernel(
   if (tid == 0) loglik[k] = ll;
 }
 
-struct Args {
-  const VissmPfDesc* d;
-  uint64_t seed, row0;
-  const float *theta, *x_start, *obs, *obs_bin;
-  const double* loglik_in;
-  double* loglik;
-  float *ll_inc, *ess, *state_end, *cloud;
-  uint64_t* q_trace;
-  int32_t* anc_trace;
-  hipStream_t st;
-  int proposal;
-};
-
-template <int MODEL, int N, int PROPOSAL>
-void launch(const Args& a) {
-  hipLaunchKernelGGL((particle_filter_kernel<MODEL, N, PROPOSAL>), dim3(a.d->K), dim3(N), 0, a.st, a.seed, a.row0,
-                     a.d->H, a.d->t0, a.d->T_total, a.d->dt, a.d->obs_std, a.theta, a.x_start, a.obs, a.obs_bin,
-                     a.loglik_in, a.loglik, a.ll_inc, a.ess, a.state_end, a.cloud,
-                     reinterpret_cast<unsigned long long*>(a.q_trace), a.anc_trace);
-}
-
-template <int MODEL, int PROPOSAL>
-void launch_n(const Args& a) {
-  switch (a.d->N) {
-    case 64: launch<MODEL, 64, PROPOSAL>(a); break;
-    case 128: launch<MODEL, 128, PROPOSAL>(a); break;
-    case 256: launch<MODEL, 256, PROPOSAL>(a); break;
-    case 512: launch<MODEL, 512, PROPOSAL>(a); break;
-    default: launch<MODEL, 1024, PROPOSAL>(a); break;
-  }
-}
-
-template <int MODEL>
-void launch_p(const Args& a) {
-  if (a.proposal == kAdapted) launch_n<MODEL, kAdapted>(a);
-  else launch_n<MODEL, kBootstrap>(a);
-}
-
 }  // namespace pfk
+
+int check_filter_args(const char* name, const VissmPfDesc* d, bool pointers, bool pointers_h) {
+  VISSM_CHECK_ARG(pf::valid_n(d->N), "%s: N=%d particles (64, 128, 256, 512 or 1024)", name, d->N);
+  VISSM_CHECK_ARG(d->K >= 0 && d->H >= 0 && d->t0 >= 0 && d->T_total >= 0, "%s: bad shape K=%d H=%d t0=%d T_total=%d",
+                  name, d->K, d->H, d->t0, d->T_total);
+  VISSM_CHECK_ARG(static_cast<int64_t>(d->K) * d->N < (int64_t{1} << 31), "%s: K N = %d %d reaches 2^31", name, d->K,
+                  d->N);
+  VISSM_CHECK_ARG(pointers, "%s: null pointer", name);
+  VISSM_CHECK_ARG(d->H == 0 || pointers_h, "%s: null pointer (H > 0)", name);
+  return VISSM_OK;
+}
+
 }  // namespace vissm
 
 using namespace vissm;
@@ -303,30 +260,31 @@ int run_filter(int proposal, const VissmPfDesc* d, uint64_t seed, uint64_t row0,
                   "particle_filter: no observation model for SV (its first coordinate is the observed series)");
   VISSM_CHECK_ARG(d->model == VISSM_MODEL_AR || d->model == VISSM_MODEL_LV || d->model == VISSM_MODEL_FHN,
                   "particle_filter: unknown model %d", d->model);
-  VISSM_CHECK_ARG(pf::valid_n(d->N), "particle_filter: N=%d particles (64, 128, 256, 512 or 1024)", d->N);
-  VISSM_CHECK_ARG(d->K >= 0 && d->H >= 0 && d->t0 >= 0 && d->T_total >= 0,
-                  "particle_filter: bad shape K=%d H=%d t0=%d T_total=%d", d->K, d->H, d->t0, d->T_total);
+  if (const int rc = check_filter_args("particle_filter", d, theta && x_start && loglik && state_end,
+                                       obs && obs_bin && ll_inc && ess))
+    return rc;
   const int S = VISSM_MODEL_S(d->model);
   VISSM_CHECK_ARG((static_cast<int64_t>(d->t0) + d->H) * S < (int64_t{1} << 31),
                   "particle_filter: (t0 + H) S = (%d + %d) %d reaches 2^31", d->t0, d->H, S);
   VISSM_CHECK_ARG(static_cast<int64_t>(d->t0) + d->H <= d->T_total,
                   "particle_filter: steps %d .. %d leave the %d observations", d->t0, d->t0 + d->H, d->T_total);
-  VISSM_CHECK_ARG(static_cast<int64_t>(d->K) * d->N < (int64_t{1} << 31), "particle_filter: K N = %d %d reaches 2^31",
-                  d->K, d->N);
   // (the conditional degenerates at obs_std = 0; a NaN fails the first comparison, an infinity the second)
   VISSM_CHECK_ARG(proposal != kAdapted || (d->obs_std > 0.f && d->obs_std <= 3.4028234e38f),
                   "particle_filter: the adapted proposal needs a positive, finite obs_std, got %g",
                   static_cast<double>(d->obs_std));
-  VISSM_CHECK_ARG(theta && x_start && loglik && state_end, "particle_filter: null pointer");
-  VISSM_CHECK_ARG(d->H == 0 || (obs && obs_bin && ll_inc && ess), "particle_filter: null pointer (H > 0)");
   if (d->K == 0) return VISSM_OK;
-  const Args a{d, seed, row0, theta, x_start, obs, obs_bin, loglik_in, loglik, ll_inc, ess, state_end, cloud, q_trace,
-               anc_trace, as_stream(stream), proposal};
-  switch (d->model) {
-    case VISSM_MODEL_AR: launch_p<VISSM_MODEL_AR>(a); break;
-    case VISSM_MODEL_LV: launch_p<VISSM_MODEL_LV>(a); break;
-    default: launch_p<VISSM_MODEL_FHN>(a); break;
-  }
+  auto launch = [&](auto model, auto n, auto prop) {
+    hipLaunchKernelGGL((particle_filter_kernel<decltype(model)::value, decltype(n)::value, decltype(prop)::value>),
+                       dim3(d->K), dim3(d->N), 0, as_stream(stream), seed, row0, d->H, d->t0, d->T_total, d->dt,
+                       d->obs_std, theta, x_start, obs, obs_bin, loglik_in, loglik, ll_inc, ess, state_end, cloud,
+                       reinterpret_cast<unsigned long long*>(q_trace), anc_trace);
+  };
+  dispatch_model(d->model, [&](auto model) {
+    dispatch_n(d->N, [&](auto n) {
+      if (proposal == kAdapted) launch(model, n, std::integral_constant<int, kAdapted>{});
+      else launch(model, n, std::integral_constant<int, kBootstrap>{});
+    });
+  });
   VISSM_CHECK_LAUNCH(proposal == kAdapted ? "particle_filter_adapted" : "particle_filter");
   return VISSM_OK;
 }

@@ -31,23 +31,6 @@
 namespace vissm {
 namespace pmk {
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
-}
-
-// inclusive scan over the wave's 64 lanes
-__device__ __forceinline__ uint64_t wave_scan(uint64_t v, int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t lo = __shfl_up(static_cast<uint32_t>(v), off, 64);
-    const uint32_t hi = __shfl_up(static_cast<uint32_t>(v >> 32), off, 64);
-    if (lane >= off) v += (static_cast<uint64_t>(hi) << 32) | lo;
-  }
-  return v;
-}
-
 // A block-uniform value the vector ALU computed, moved to a scalar register: the chain's state and the proposal live
 // across the whole filter loop, where the 1024-lane block has no vector registers to spare for them.
 __device__ __forceinline__ float uni(float v) {
@@ -241,34 +224,6 @@ __global__ __launch_bounds__(N) void pmmh_kernel(uint64_t seed, uint64_t row0, i
   }
 }
 
-struct Args {
-  const VissmPmmhDesc* d;
-  uint64_t seed, row0;
-  const float* theta_cur;
-  const double* ll_cur;
-  const float *prop_chol, *prior, *x_start, *obs, *obs_bin;
-  Out o;
-  hipStream_t st;
-};
-
-template <int MODEL, int N>
-void launch(const Args& a) {
-  hipLaunchKernelGGL((pmmh_kernel<MODEL, N>), dim3(a.d->C), dim3(N), 0, a.st, a.seed, a.row0, a.d->C, a.d->n_iter,
-                     a.d->it0, a.d->T_total, a.d->dt, a.d->obs_std, a.theta_cur, a.ll_cur, a.prop_chol, a.prior,
-                     a.x_start, a.obs, a.obs_bin, a.o);
-}
-
-template <int MODEL>
-void launch_n(const Args& a) {
-  switch (a.d->N) {
-    case 64: launch<MODEL, 64>(a); break;
-    case 128: launch<MODEL, 128>(a); break;
-    case 256: launch<MODEL, 256>(a); break;
-    case 512: launch<MODEL, 512>(a); break;
-    default: launch<MODEL, 1024>(a); break;
-  }
-}
-
 // ---- stochastic volatility ----------------------------------------------------------------------------------------
 // The same iteration shell around sv_filter_kernel's loop (sv_filter.hip) with t0 = 0 and H = T_total: the particle is
 // the latent h alone, the observed series y [T_total + 1] the state's first coordinate.  Every step is observed: step
@@ -416,21 +371,16 @@ __global__ __launch_bounds__(N) void sv_pmmh_kernel(uint64_t seed, uint64_t row0
   }
 }
 
-struct SvArgs {
-  const VissmPmmhDesc* d;
-  uint64_t seed, row0;
-  const float* theta_cur;
-  const double* ll_cur;
-  const float *prop_chol, *prior, *h_start, *obs;
-  Out o;
-  hipStream_t st;
-};
-
-template <int N>
-void launch_sv(const SvArgs& a) {
-  hipLaunchKernelGGL((sv_pmmh_kernel<N>), dim3(a.d->C), dim3(N), 0, a.st, a.seed, a.row0, a.d->C, a.d->n_iter,
-                     a.d->it0, a.d->T_total, a.d->dt, a.theta_cur, a.ll_cur, a.prop_chol, a.prior, a.h_start, a.obs,
-                     a.o);
+// the checks the two entries share, with the entry's name in the message
+int check_chain_args(const char* name, const VissmPmmhDesc* d, bool pointers, bool pointers_iter, bool pointers_t) {
+  VISSM_CHECK_ARG(pf::valid_n(d->N), "%s: N=%d particles (64, 128, 256, 512 or 1024)", name, d->N);
+  VISSM_CHECK_ARG(d->C >= 1, "%s: C=%d chains (at least one)", name, d->C);
+  VISSM_CHECK_ARG(d->n_iter >= 0 && d->it0 >= 0 && static_cast<int64_t>(d->it0) + d->n_iter < (int64_t{1} << 31),
+                  "%s: bad iterations it0=%d n_iter=%d", name, d->it0, d->n_iter);
+  VISSM_CHECK_ARG(pointers, "%s: null pointer", name);
+  VISSM_CHECK_ARG(d->n_iter == 0 || pointers_iter, "%s: null pointer (n_iter > 0)", name);
+  VISSM_CHECK_ARG(d->T_total <= 0 || pointers_t, "%s: null pointer (T_total > 0)", name);
+  return VISSM_OK;
 }
 
 }  // namespace pmk
@@ -455,10 +405,9 @@ extern "C" int vissm_pmmh(const VissmPmmhDesc* d, uint64_t seed, uint64_t row0, 
                   "pmmh: no observation model for SV (its first coordinate is the observed series)");
   VISSM_CHECK_ARG(d->model == VISSM_MODEL_AR || d->model == VISSM_MODEL_LV || d->model == VISSM_MODEL_FHN,
                   "pmmh: unknown model %d", d->model);
-  VISSM_CHECK_ARG(pf::valid_n(d->N), "pmmh: N=%d particles (64, 128, 256, 512 or 1024)", d->N);
-  VISSM_CHECK_ARG(d->C >= 1, "pmmh: C=%d chains (at least one)", d->C);
-  VISSM_CHECK_ARG(d->n_iter >= 0 && d->it0 >= 0 && static_cast<int64_t>(d->it0) + d->n_iter < (int64_t{1} << 31),
-                  "pmmh: bad iterations it0=%d n_iter=%d", d->it0, d->n_iter);
+  if (const int rc = check_chain_args("pmmh", d, theta_cur && ll_cur && prop_chol && prior && x_start && theta_end && ll_end,
+                                      theta_chain && ll_chain && accept, obs && obs_bin))
+    return rc;
   VISSM_CHECK_ARG(d->T_total >= 0, "pmmh: T_total=%d", d->T_total);
   const int S = VISSM_MODEL_S(d->model);
   VISSM_CHECK_ARG(static_cast<int64_t>(d->T_total) * S < (int64_t{1} << 31), "pmmh: T_total S = %d %d reaches 2^31",
@@ -466,17 +415,14 @@ extern "C" int vissm_pmmh(const VissmPmmhDesc* d, uint64_t seed, uint64_t row0, 
   // (a NaN fails the first comparison, an infinity the second)
   VISSM_CHECK_ARG(d->obs_std > 0.f && d->obs_std <= 3.4028234e38f,
                   "pmmh: a positive, finite obs_std expected, got %g", static_cast<double>(d->obs_std));
-  VISSM_CHECK_ARG(theta_cur && ll_cur && prop_chol && prior && x_start && theta_end && ll_end, "pmmh: null pointer");
-  VISSM_CHECK_ARG(d->n_iter == 0 || (theta_chain && ll_chain && accept), "pmmh: null pointer (n_iter > 0)");
-  VISSM_CHECK_ARG(d->T_total == 0 || (obs && obs_bin), "pmmh: null pointer (T_total > 0)");
-  const Args a{d,   seed,    row0, theta_cur, ll_cur, prop_chol, prior,
-               x_start, obs, obs_bin,
-               Out{theta_chain, ll_chain, accept, theta_end, ll_end, theta_prop, ll_prop, logu}, as_stream(stream)};
-  switch (d->model) {
-    case VISSM_MODEL_AR: launch_n<VISSM_MODEL_AR>(a); break;
-    case VISSM_MODEL_LV: launch_n<VISSM_MODEL_LV>(a); break;
-    default: launch_n<VISSM_MODEL_FHN>(a); break;
-  }
+  const Out o{theta_chain, ll_chain, accept, theta_end, ll_end, theta_prop, ll_prop, logu};
+  dispatch_model(d->model, [&](auto model) {
+    dispatch_n(d->N, [&](auto n) {
+      hipLaunchKernelGGL((pmmh_kernel<decltype(model)::value, decltype(n)::value>), dim3(d->C), dim3(d->N), 0,
+                         as_stream(stream), seed, row0, d->C, d->n_iter, d->it0, d->T_total, d->dt, d->obs_std,
+                         theta_cur, ll_cur, prop_chol, prior, x_start, obs, obs_bin, o);
+    });
+  });
   VISSM_CHECK_LAUNCH("pmmh");
   return VISSM_OK;
 }
@@ -493,29 +439,20 @@ extern "C" int vissm_sv_pmmh(const VissmPmmhDesc* d, uint64_t seed, uint64_t row
   // host arithmetic only, before any GPU call
   VISSM_CHECK_ARG(d, "sv_pmmh: null descriptor");
   VISSM_CHECK_ARG(d->model == VISSM_MODEL_SV, "sv_pmmh: model %d is not SV (vissm_pmmh has the others)", d->model);
-  VISSM_CHECK_ARG(pf::valid_n(d->N), "sv_pmmh: N=%d particles (64, 128, 256, 512 or 1024)", d->N);
-  VISSM_CHECK_ARG(d->C >= 1, "sv_pmmh: C=%d chains (at least one)", d->C);
-  VISSM_CHECK_ARG(d->n_iter >= 0 && d->it0 >= 0 && static_cast<int64_t>(d->it0) + d->n_iter < (int64_t{1} << 31),
-                  "sv_pmmh: bad iterations it0=%d n_iter=%d", d->it0, d->n_iter);
+  if (const int rc = check_chain_args("sv_pmmh", d, theta_cur && ll_cur && prop_chol && prior && h_start && theta_end && ll_end,
+                                      theta_chain && ll_chain && accept, obs != nullptr))
+    return rc;
   // (the series holds T_total + 1 values and step ta reads y[ta + 1])
   VISSM_CHECK_ARG(d->T_total >= 0 && d->T_total < 2147483647, "sv_pmmh: T_total=%d", d->T_total);
   // (a NaN fails the first comparison, an infinity the second)
   VISSM_CHECK_ARG(d->dt > 0.f && d->dt <= 3.4028234e38f, "sv_pmmh: dt must be positive and finite, got %g",
                   static_cast<double>(d->dt));
-  VISSM_CHECK_ARG(theta_cur && ll_cur && prop_chol && prior && h_start && theta_end && ll_end,
-                  "sv_pmmh: null pointer");
-  VISSM_CHECK_ARG(d->n_iter == 0 || (theta_chain && ll_chain && accept), "sv_pmmh: null pointer (n_iter > 0)");
-  VISSM_CHECK_ARG(d->T_total == 0 || obs, "sv_pmmh: null pointer (T_total > 0)");
-  const SvArgs a{d,   seed, row0, theta_cur, ll_cur, prop_chol, prior, h_start,
-                 obs, Out{theta_chain, ll_chain, accept, theta_end, ll_end, theta_prop, ll_prop, logu},
-                 as_stream(stream)};
-  switch (d->N) {
-    case 64: launch_sv<64>(a); break;
-    case 128: launch_sv<128>(a); break;
-    case 256: launch_sv<256>(a); break;
-    case 512: launch_sv<512>(a); break;
-    default: launch_sv<1024>(a); break;
-  }
+  const Out o{theta_chain, ll_chain, accept, theta_end, ll_end, theta_prop, ll_prop, logu};
+  dispatch_n(d->N, [&](auto n) {
+    hipLaunchKernelGGL((sv_pmmh_kernel<decltype(n)::value>), dim3(d->C), dim3(d->N), 0, as_stream(stream), seed, row0,
+                       d->C, d->n_iter, d->it0, d->T_total, d->dt, theta_cur, ll_cur, prop_chol, prior, h_start, obs,
+                       o);
+  });
   VISSM_CHECK_LAUNCH("sv_pmmh");
   return VISSM_OK;
 }

@@ -247,35 +247,6 @@ __global__ __launch_bounds__(kLanes* block_waves(N)) void particle_smooth_kernel
   }
 }
 
-struct Args {
-  const VissmPsDesc* d;
-  uint64_t seed, row0;
-  const float *theta, *cloud, *x_next;
-  float *paths, *x_first;
-  int32_t* idx;
-  uint64_t* q_trace;
-  hipStream_t st;
-};
-
-template <int MODEL, int N>
-void launch(const Args& a) {
-  hipLaunchKernelGGL((particle_smooth_kernel<MODEL, N>), dim3(a.d->M / kLanes, a.d->K), dim3(kLanes * block_waves(N)), 0,
-                     a.st, a.seed,
-                     a.row0, a.d->M, a.d->H, a.d->t0, a.d->dt, a.theta, a.cloud, a.x_next, a.paths, a.x_first, a.idx,
-                     reinterpret_cast<unsigned long long*>(a.q_trace));
-}
-
-template <int MODEL>
-void launch_n(const Args& a) {
-  switch (a.d->N) {
-    case 64: launch<MODEL, 64>(a); break;
-    case 128: launch<MODEL, 128>(a); break;
-    case 256: launch<MODEL, 256>(a); break;
-    case 512: launch<MODEL, 512>(a); break;
-    default: launch<MODEL, 1024>(a); break;
-  }
-}
-
 }  // namespace psk
 }  // namespace vissm
 
@@ -309,12 +280,14 @@ extern "C" int vissm_particle_smooth(const VissmPsDesc* d, uint64_t seed, uint64
                   "particle_smooth: t0 + H = %d + %d reaches 2^31", d->t0, d->H);
   VISSM_CHECK_ARG(theta && cloud && paths && x_first, "particle_smooth: null pointer");
   if (d->K == 0) return VISSM_OK;
-  const Args a{d, seed, row0, theta, cloud, x_next, paths, x_first, idx, q_trace, as_stream(stream)};
-  switch (d->model) {
-    case VISSM_MODEL_AR: launch_n<VISSM_MODEL_AR>(a); break;
-    case VISSM_MODEL_LV: launch_n<VISSM_MODEL_LV>(a); break;
-    default: launch_n<VISSM_MODEL_FHN>(a); break;
-  }
+  dispatch_model(d->model, [&](auto model) {
+    dispatch_n(d->N, [&](auto n) {
+      constexpr int N = decltype(n)::value;
+      hipLaunchKernelGGL((particle_smooth_kernel<decltype(model)::value, N>), dim3(d->M / kLanes, d->K),
+                         dim3(kLanes * block_waves(N)), 0, as_stream(stream), seed, row0, d->M, d->H, d->t0, d->dt,
+                         theta, cloud, x_next, paths, x_first, idx, reinterpret_cast<unsigned long long*>(q_trace));
+    });
+  });
   VISSM_CHECK_LAUNCH("particle_smooth");
   return VISSM_OK;
 }

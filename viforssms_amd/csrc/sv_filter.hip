@@ -33,23 +33,6 @@ constexpr int tile_depth(int N) {
   return d > 64 ? 64 : d;
 }
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
-}
-
-// inclusive scan over the wave's 64 lanes
-__device__ __forceinline__ uint64_t wave_scan(uint64_t v, int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t lo = __shfl_up(static_cast<uint32_t>(v), off, 64);
-    const uint32_t hi = __shfl_up(static_cast<uint32_t>(v >> 32), off, 64);
-    if (lane >= off) v += (static_cast<uint64_t>(hi) << 32) | lo;
-  }
-  return v;
-}
-
 template <int N>
 __global__ __launch_bounds__(N) void sv_filter_kernel(
     uint64_t seed, uint64_t row0, int H, int t0, float dt, const float* __restrict__ theta,
@@ -178,25 +161,6 @@ __global__ __launch_bounds__(N) void sv_filter_kernel(
   }
   state_end[p] = h;
   if (tid == 0) loglik[k] = ll;
-}
-
-struct FArgs {
-  const VissmPfDesc* d;
-  uint64_t seed, row0;
-  const float *theta, *x_start, *obs;
-  const double* loglik_in;
-  double* loglik;
-  float *ll_inc, *ess, *state_end, *cloud;
-  uint64_t* q_trace;
-  int32_t* anc_trace;
-  hipStream_t st;
-};
-
-template <int N>
-void launch_filter(const FArgs& a) {
-  hipLaunchKernelGGL((sv_filter_kernel<N>), dim3(a.d->K), dim3(N), 0, a.st, a.seed, a.row0, a.d->H, a.d->t0, a.d->dt,
-                     a.theta, a.x_start, a.obs, a.loglik_in, a.loglik, a.ll_inc, a.ess, a.state_end, a.cloud,
-                     reinterpret_cast<unsigned long long*>(a.q_trace), a.anc_trace);
 }
 
 // ---- smoother -----------------------------------------------------------------------------------------------------
@@ -388,23 +352,6 @@ __global__ __launch_bounds__(kLanes* block_waves(N)) void sv_smooth_kernel(
   if (wv == 0) x_first[traj] = xt;
 }
 
-struct SArgs {
-  const VissmPsDesc* d;
-  uint64_t seed, row0;
-  const float *theta, *cloud, *obs, *x_next;
-  float *paths, *x_first;
-  int32_t* idx;
-  uint64_t* q_trace;
-  hipStream_t st;
-};
-
-template <int N>
-void launch_smooth(const SArgs& a) {
-  hipLaunchKernelGGL((sv_smooth_kernel<N>), dim3(a.d->M / kLanes, a.d->K), dim3(kLanes * block_waves(N)), 0, a.st,
-                     a.seed, a.row0, a.d->M, a.d->H, a.d->t0, a.d->dt, a.theta, a.cloud, a.obs, a.x_next, a.paths,
-                     a.x_first, a.idx, reinterpret_cast<unsigned long long*>(a.q_trace));
-}
-
 }  // namespace svk
 }  // namespace vissm
 
@@ -425,30 +372,21 @@ extern "C" int vissm_sv_filter(const VissmPfDesc* d, uint64_t seed, uint64_t row
   VISSM_CHECK_ARG(d, "sv_filter: null descriptor");
   VISSM_CHECK_ARG(d->model == VISSM_MODEL_SV, "sv_filter: model %d is not SV (vissm_particle_filter has the others)",
                   d->model);
-  VISSM_CHECK_ARG(pf::valid_n(d->N), "sv_filter: N=%d particles (64, 128, 256, 512 or 1024)", d->N);
-  VISSM_CHECK_ARG(d->K >= 0 && d->H >= 0 && d->t0 >= 0 && d->T_total >= 0,
-                  "sv_filter: bad shape K=%d H=%d t0=%d T_total=%d", d->K, d->H, d->t0, d->T_total);
+  if (const int rc = check_filter_args("sv_filter", d, theta && x_start && loglik && state_end, obs && ll_inc && ess))
+    return rc;
   VISSM_CHECK_ARG(static_cast<int64_t>(d->t0) + d->H < (int64_t{1} << 31), "sv_filter: t0 + H = %d + %d reaches 2^31",
                   d->t0, d->H);
   VISSM_CHECK_ARG(static_cast<int64_t>(d->t0) + d->H <= d->T_total,
                   "sv_filter: steps %d .. %d leave the %d transitions of the series", d->t0, d->t0 + d->H, d->T_total);
-  VISSM_CHECK_ARG(static_cast<int64_t>(d->K) * d->N < (int64_t{1} << 31), "sv_filter: K N = %d %d reaches 2^31", d->K,
-                  d->N);
   // (a NaN fails the first comparison, an infinity the second)
   VISSM_CHECK_ARG(d->dt > 0.f && d->dt <= 3.4028234e38f, "sv_filter: dt must be positive and finite, got %g",
                   static_cast<double>(d->dt));
-  VISSM_CHECK_ARG(theta && x_start && loglik && state_end, "sv_filter: null pointer");
-  VISSM_CHECK_ARG(d->H == 0 || (obs && ll_inc && ess), "sv_filter: null pointer (H > 0)");
   if (d->K == 0) return VISSM_OK;
-  const FArgs a{d, seed, row0, theta, x_start, obs, loglik_in, loglik, ll_inc, ess, state_end, cloud, q_trace, anc_trace,
-                as_stream(stream)};
-  switch (d->N) {
-    case 64: launch_filter<64>(a); break;
-    case 128: launch_filter<128>(a); break;
-    case 256: launch_filter<256>(a); break;
-    case 512: launch_filter<512>(a); break;
-    default: launch_filter<1024>(a); break;
-  }
+  dispatch_n(d->N, [&](auto n) {
+    hipLaunchKernelGGL((sv_filter_kernel<decltype(n)::value>), dim3(d->K), dim3(d->N), 0, as_stream(stream), seed, row0,
+                       d->H, d->t0, d->dt, theta, x_start, obs, loglik_in, loglik, ll_inc, ess, state_end, cloud,
+                       reinterpret_cast<unsigned long long*>(q_trace), anc_trace);
+  });
   VISSM_CHECK_LAUNCH("sv_filter");
   return VISSM_OK;
 }
@@ -482,14 +420,12 @@ extern "C" int vissm_sv_smooth(const VissmPsDesc* d, uint64_t seed, uint64_t row
                   static_cast<double>(d->dt));
   VISSM_CHECK_ARG(theta && cloud && obs && paths && x_first, "sv_smooth: null pointer");
   if (d->K == 0) return VISSM_OK;
-  const SArgs a{d, seed, row0, theta, cloud, obs, x_next, paths, x_first, idx, q_trace, as_stream(stream)};
-  switch (d->N) {
-    case 64: launch_smooth<64>(a); break;
-    case 128: launch_smooth<128>(a); break;
-    case 256: launch_smooth<256>(a); break;
-    case 512: launch_smooth<512>(a); break;
-    default: launch_smooth<1024>(a); break;
-  }
+  dispatch_n(d->N, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    hipLaunchKernelGGL((sv_smooth_kernel<N>), dim3(d->M / kLanes, d->K), dim3(kLanes * block_waves(N)), 0,
+                       as_stream(stream), seed, row0, d->M, d->H, d->t0, d->dt, theta, cloud, obs, x_next, paths,
+                       x_first, idx, reinterpret_cast<unsigned long long*>(q_trace));
+  });
   VISSM_CHECK_LAUNCH("sv_smooth");
   return VISSM_OK;
 }
