@@ -873,6 +873,68 @@ int vissm_sv_pmmh(const VissmPmmhDesc* d, uint64_t seed, uint64_t row0,
                   double* logu /* [C][n_iter] or NULL */, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Adaptive particle marginal Metropolis-Hastings: vissm_pmmh / vissm_sv_pmmh with a proposal factor per chain that
+ * the chain learns itself (robust adaptive Metropolis, Vihola 2012) while its absolute iteration i is below adapt_end,
+ * and keeps frozen from adapt_end on.  The draws after adapt_end come from an ordinary fixed-proposal chain, which
+ * targets p(theta | y) exactly; those before are a burn-in.  Everything the twins' blocks state holds unchanged: the
+ * rows, the words, theta' (with L = the chain's factor of that iteration), lp, ll', the decision, the outputs and the
+ * refusals.  chol_in [C][P][P] fp32 holds one lower factor per chain (the strict upper part is ignored).  After the
+ * decision of an iteration i < adapt_end (csrc/mh_math.hpp, all in double):
+ *   alpha  = 0 if r is NaN, 1 if r >= 0, else exp(r), with r = (ll' - ll) + (lp' - lp) of the state before the decision
+ *            (a dead proposal gives 0, a chain at -inf meeting a finite proposal 1)
+ *   eta    = min(1, P (i + 1)^-gamma),  d = eta (alpha - target_accept),  n2 = sum_{j < P} xi_j^2 (ascending j)
+ *   skip   L is unchanged if !(n2 > 0), d == 0 or d is not finite
+ *   v_p    = (sum_{j <= p} L_pj xi_j) sqrt(|d| / n2) (ascending j from 0.0),  sgn = the sign of d
+ *   pass   for k = 0 .. P - 1:  r2 = L_kk^2 + sgn v_k^2 (L is unchanged if !(L_kk > 0) or !(r2 > 0));  rho = sqrt(r2),
+ *            c = rho / L_kk, t = v_k / L_kk, L_kk = rho;  for i > k: L_ik = (L_ik + sgn t v_i) / c, then
+ *            v_i = c v_i - t L_ik with the new L_ik
+ *   round  every entry to fp32; if one is not finite or a diagonal entry is <= 0, L is unchanged as a whole
+ * so L' L'^T = L (I + d xi xi^T / |xi|^2) L^T up to the fp32 rounding of the factor, positive definite as |d| < 1.
+ * The factor is fp32 after every update: a frozen chain is bit for bit the twin's chain with prop_chol = its factor,
+ * and adapt_end = 0 with every chain's factor equal is the twin.
+ *
+ * chol_end [C][P][P] is the factor after the last iteration (the strict upper part written 0): a call with it0' = it0 +
+ * n_iter, theta_cur = theta_end, ll_cur = ll_end, chol_in = chol_end and the same adapt_end, target_accept and gamma
+ * continues bitwise, across adapt_end too.  Optional traces for tests, NULL in production, beside the twins':
+ * xi_trace [C][n_iter][8] fp32 the iteration's normals as the device drew them; alpha_trace and eta_trace [C][n_iter]
+ * double (eta = 0 from adapt_end on); chol_trace [C][n_iter][P][P] fp32 the factor after the iteration.  The factor
+ * lives in LDS and thread 0 updates it; no atomics, no workspace, nothing crosses blocks: chain c's bits depend on the
+ * block index through r only.  Refused by host arithmetic (VISSM_EINVAL): what the twin refuses, adapt_end < 0,
+ * target_accept outside (0, 1), gamma outside (0, 1] (a NaN is outside), a null chol_in or chol_end.
+ * vissm_pmmh_adaptive_lds_bytes / vissm_sv_pmmh_adaptive_lds_bytes: the LDS one block declares, the twin's +
+ * 8 (P P + 2 P) (the update's doubles) + 8 ceil(P P / 2) (the factor, in whole doubles): 8 N + 4 S N + 192 + 160 for
+ * P = 3, + 256 for P = 4, + 384 for P = 5, and 8 N + 4 N + 192 + 256 for SV (host arithmetic; 0 = bad model or N).
+ * ------------------------------------------------------------------------- */
+int32_t vissm_pmmh_adaptive_lds_bytes(int32_t model, int32_t N);
+int vissm_pmmh_adaptive(const VissmPmmhDesc* d, uint64_t seed, uint64_t row0,
+                        const float* theta_cur /* [C][P] */, const double* ll_cur /* [C] */,
+                        const float* chol_in /* [C][P][P] lower */, const float* prior /* [P][2] (mean, sd) */,
+                        const float* x_start /* [S] */, const float* obs /* [S][T_total] */,
+                        const float* obs_bin /* [S][T_total] */,
+                        int32_t adapt_end, double target_accept, double gamma,
+                        float* theta_chain /* [C][n_iter][P] */, double* ll_chain /* [C][n_iter] */,
+                        int32_t* accept /* [C][n_iter] */, float* theta_end /* [C][P] */, double* ll_end /* [C] */,
+                        float* chol_end /* [C][P][P] */,
+                        float* theta_prop /* [C][n_iter][P] or NULL */, double* ll_prop /* [C][n_iter] or NULL */,
+                        double* logu /* [C][n_iter] or NULL */, float* xi_trace /* [C][n_iter][8] or NULL */,
+                        double* alpha_trace /* [C][n_iter] or NULL */, double* eta_trace /* [C][n_iter] or NULL */,
+                        float* chol_trace /* [C][n_iter][P][P] or NULL */, void* stream);
+
+int32_t vissm_sv_pmmh_adaptive_lds_bytes(int32_t N);
+int vissm_sv_pmmh_adaptive(const VissmPmmhDesc* d, uint64_t seed, uint64_t row0,
+                           const float* theta_cur /* [C][4] */, const double* ll_cur /* [C] */,
+                           const float* chol_in /* [C][4][4] lower */, const float* prior /* [4][2] (mean, sd) */,
+                           const float* h_start /* [1] */, const float* obs /* y[0 .. T_total] */,
+                           int32_t adapt_end, double target_accept, double gamma,
+                           float* theta_chain /* [C][n_iter][4] */, double* ll_chain /* [C][n_iter] */,
+                           int32_t* accept /* [C][n_iter] */, float* theta_end /* [C][4] */, double* ll_end /* [C] */,
+                           float* chol_end /* [C][4][4] */,
+                           float* theta_prop /* [C][n_iter][4] or NULL */, double* ll_prop /* [C][n_iter] or NULL */,
+                           double* logu /* [C][n_iter] or NULL */, float* xi_trace /* [C][n_iter][8] or NULL */,
+                           double* alpha_trace /* [C][n_iter] or NULL */, double* eta_trace /* [C][n_iter] or NULL */,
+                           float* chol_trace /* [C][n_iter][4][4] or NULL */, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Opt-in kernel timing (for bench.py's live roofline): when enabled, the flow
  * entry points bracket their main kernel with hipEvents on the launch stream.
  * kind: VISSM_PROF_FLOW_FWD / VISSM_PROF_FLOW_BWD (flow kernels),

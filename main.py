@@ -60,8 +60,10 @@ def run(argv=None):
         model.save_smoother(args.smooth[3], args.smooth[0], args.smooth[1], args.smooth[2],
                             proposal=args.filter_proposal)   # as the filter
     if args.mcmc:
-        # every rank the same launches; rank 0 writes.  A quarter of the iterations is burn-in, as the default's
-        model.save_theta_mcmc(args.mcmc[3], args.mcmc[0], args.mcmc[1], args.mcmc[2], burn_in=args.mcmc[2] // 4)
+        # every rank the same launches; rank 0 writes.  A quarter of the iterations is burn-in, as the default's; with
+        # --mcmc-adapt the chains adapt their proposals over the first half and the second half is kept
+        model.save_theta_mcmc(args.mcmc[3], args.mcmc[0], args.mcmc[1], args.mcmc[2],
+                              burn_in=args.mcmc[2] // (2 if args.mcmc_adapt else 4), adapt=args.mcmc_adapt)
     return model
 
 

@@ -18,7 +18,11 @@ do the same work; their random numbers differ, so the chains agree in distributi
 kernel's acceptance rate over the window, and the seconds of one launch of diagnostics.MCMC_LAUNCH_STEPS filter steps
 per block (max(1, MCMC_LAUNCH_STEPS // T) iterations) at C = 64.
 
-    python scripts/bench_pmmh.py [--runs 5] [--iters 4] [--iters-short 100] [--out FILE.json]
+With --adaptive the adaptive kernel (ops.pmmh_adaptive: the same chains, the shared factor tiled, every iteration of
+the window adapting) is timed beside its twin in the same alternating runs, in place of the host loop: per iteration
+the median and the range of both, and their ratio.
+
+    python scripts/bench_pmmh.py [--runs 5] [--iters 4] [--iters-short 100] [--adaptive] [--out FILE.json]
 """
 import argparse
 import json
@@ -67,6 +71,12 @@ def fused(s, C, ll, n_iter):
                     n_iter, SEED, C * N)
 
 
+def adaptive(s, C, ll, n_iter):
+    from viforssms_amd import ops
+    return ops.pmmh_adaptive(s["model"], s["th"], ll, s["L"].repeat(C, 1, 1), s["prior"], s["x0"], s["obs"],
+                             s["obs_bin"], s["dt"], s["sd"], N, n_iter, SEED, C * N, n_iter)
+
+
 def loop(s, C, ll, n_iter, x_rows):
     from viforssms_amd import ops
     th, lp = s["th"], -0.5 * (((s["th"] - s["prior"][:, 0]) / s["prior"][:, 1]).double() ** 2).sum(1)
@@ -82,12 +92,14 @@ def loop(s, C, ll, n_iter, x_rows):
     return th, ll
 
 
-def bench_shape(shape, C, runs, n_iter):
+def bench_shape(shape, C, runs, n_iter, with_adaptive=False):
     from viforssms_amd import _lib, diagnostics
     s = setup(shape, C)
     ll = initial_ll(s, C)
     x_rows = s["x0"].unsqueeze(0).expand(C * N, -1).contiguous()
     fns = {"fused": lambda: fused(s, C, ll, n_iter), "loop": lambda: loop(s, C, ll, n_iter, x_rows)}
+    if with_adaptive:
+        fns = {"fused": fns["fused"], "adaptive": lambda: adaptive(s, C, ll, n_iter)}
     for f in fns.values():
         f()
     ms = {k: [] for k in fns}
@@ -100,6 +112,11 @@ def bench_shape(shape, C, runs, n_iter):
            "per_iteration": {k: stats(v) for k, v in ms.items()},
            "fused_acceptance": float(r.accept.double().mean()),
            "fused_finite_ll": bool(torch.isfinite(r.ll_chain).all())}
+    if with_adaptive:
+        res["adaptive_over_fused"] = (res["per_iteration"]["adaptive"]["median_ms"] /
+                                      res["per_iteration"]["fused"]["median_ms"])
+        res["adaptive_lds_bytes_per_block"] = int(_lib.load().vissm_pmmh_adaptive_lds_bytes(s["model"], N))
+        return res
     res["loop_over_fused"] = res["per_iteration"]["loop"]["median_ms"] / res["per_iteration"]["fused"]["median_ms"]
     res["us_per_filter_step_fused"] = 1e3 * res["per_iteration"]["fused"]["median_ms"] / max(s["T"], 1)
     if C == 64:
@@ -115,11 +132,12 @@ def main():
     ap.add_argument("--iters-short", type=int, default=100, help="iterations per timed window at ar64")
     ap.add_argument("--shapes", default="ar,lv,ar64")
     ap.add_argument("--chains", default="64,256")
+    ap.add_argument("--adaptive", action="store_true", help="time ops.pmmh_adaptive beside ops.pmmh, not the host loop")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_pmmh.py needs the GPU: there is nothing to time without it")
-    res = {"cases": [bench_shape(sh, int(c), args.runs, args.iters_short if sh == "ar64" else args.iters)
+    res = {"cases": [bench_shape(sh, int(c), args.runs, args.iters_short if sh == "ar64" else args.iters, args.adaptive)
                      for sh in args.shapes.split(",") for c in args.chains.split(",")]}
     line = json.dumps(res)
     print(line)

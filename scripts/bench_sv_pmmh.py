@@ -18,7 +18,11 @@ filter entry alone (one ops.sv_filter(cloud=False) call for K = C, per step, fro
 acceptance rate over the window, and the seconds of one launch of diagnostics.MCMC_LAUNCH_STEPS filter steps per block
 (max(1, MCMC_LAUNCH_STEPS // T) iterations) at C = 64.
 
-    python scripts/bench_sv_pmmh.py [--runs 5] [--iters 8] [--iters-short 100] [--out FILE.json]
+With --adaptive the adaptive kernel (ops.sv_pmmh_adaptive: the same chains, the shared factor tiled, every iteration
+of the window adapting) is timed beside its twin in the same alternating runs, in place of the host loop and the filter
+entry: per iteration the median and the range of both, and their ratio.
+
+    python scripts/bench_sv_pmmh.py [--runs 5] [--iters 8] [--iters-short 100] [--adaptive] [--out FILE.json]
 """
 import argparse
 import json
@@ -62,6 +66,12 @@ def fused(s, C, ll, n_iter):
     return ops.sv_pmmh(s["th"], ll, s["L"], s["prior"], s["h0"], s["y"], DT, N, n_iter, SEED, C * N)
 
 
+def adaptive(s, C, ll, n_iter):
+    from viforssms_amd import ops
+    return ops.sv_pmmh_adaptive(s["th"], ll, s["L"].repeat(C, 1, 1), s["prior"], s["h0"], s["y"], DT, N, n_iter, SEED,
+                                C * N, n_iter)
+
+
 def loop(s, C, ll, n_iter, h_rows):
     th, lp = s["th"], -0.5 * (((s["th"] - s["prior"][:, 0]) / s["prior"][:, 1]).double() ** 2).sum(1)
     Lt = s["L"].t().contiguous()
@@ -75,13 +85,15 @@ def loop(s, C, ll, n_iter, h_rows):
     return th, ll
 
 
-def bench_shape(shape, C, runs, n_iter):
+def bench_shape(shape, C, runs, n_iter, with_adaptive=False):
     from viforssms_amd import _lib, diagnostics
     s = setup(shape, C)
     h_rows = s["h0"].expand(C * N).contiguous()
     ll = filter_ll(s, s["th"], h_rows, 0)
     fns = {"fused": lambda: fused(s, C, ll, n_iter), "loop": lambda: loop(s, C, ll, n_iter, h_rows),
            "filter": lambda: [filter_ll(s, s["th"], h_rows, 0) for _ in range(n_iter)]}
+    if with_adaptive:
+        fns = {"fused": fns["fused"], "adaptive": lambda: adaptive(s, C, ll, n_iter)}
     for f in fns.values():
         f()
     ms = {k: [] for k in fns}
@@ -96,6 +108,10 @@ def bench_shape(shape, C, runs, n_iter):
            "fused_acceptance": float(r.accept.double().mean()),
            "fused_finite_ll": bool(torch.isfinite(r.ll_chain).all())}
     med = lambda k: res["per_iteration"][k]["median_ms"]
+    if with_adaptive:
+        res["adaptive_over_fused"] = med("adaptive") / med("fused")
+        res["adaptive_lds_bytes_per_block"] = int(_lib.load().vissm_sv_pmmh_adaptive_lds_bytes(N))
+        return res
     res["loop_over_fused"] = med("loop") / med("fused")
     res["us_per_filter_step_fused"] = 1e3 * med("fused") / T
     res["us_per_filter_step_sv_filter_entry"] = 1e3 * med("filter") / T
@@ -112,11 +128,13 @@ def main():
     ap.add_argument("--iters-short", type=int, default=100, help="iterations per timed window at T = 64")
     ap.add_argument("--shapes", default="sv,sv64")
     ap.add_argument("--chains", default="64,256")
+    ap.add_argument("--adaptive", action="store_true",
+                    help="time ops.sv_pmmh_adaptive beside ops.sv_pmmh, not the host loop and the filter entry")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_sv_pmmh.py needs the GPU: there is nothing to time without it")
-    res = {"cases": [bench_shape(sh, int(c), args.runs, args.iters_short if sh == "sv64" else args.iters)
+    res = {"cases": [bench_shape(sh, int(c), args.runs, args.iters_short if sh == "sv64" else args.iters, args.adaptive)
                      for sh in args.shapes.split(",") for c in args.chains.split(",")]}
     line = json.dumps(res)
     print(line)

@@ -228,6 +228,12 @@ SIGNATURES = {
     "vissm_pmmh": (_i32, [ctypes.POINTER(PmmhDesc), _u64, _u64] + [_c_void_p] * 15 + [_c_void_p]),
     "vissm_sv_pmmh_lds_bytes": (_i32, [_i32]),
     "vissm_sv_pmmh": (_i32, [ctypes.POINTER(PmmhDesc), _u64, _u64] + [_c_void_p] * 14 + [_c_void_p]),
+    "vissm_pmmh_adaptive_lds_bytes": (_i32, [_i32, _i32]),
+    "vissm_pmmh_adaptive": (_i32, [ctypes.POINTER(PmmhDesc), _u64, _u64] + [_c_void_p] * 7 +
+                            [_i32, ctypes.c_double, ctypes.c_double] + [_c_void_p] * 13 + [_c_void_p]),
+    "vissm_sv_pmmh_adaptive_lds_bytes": (_i32, [_i32]),
+    "vissm_sv_pmmh_adaptive": (_i32, [ctypes.POINTER(PmmhDesc), _u64, _u64] + [_c_void_p] * 6 +
+                               [_i32, ctypes.c_double, ctypes.c_double] + [_c_void_p] * 13 + [_c_void_p]),
     "vissm_sv_smooth": (_i32, [ctypes.POINTER(PsDesc), _u64, _u64] + [_c_void_p] * 3 + [_i32] + [_c_void_p] * 5 +
                         [_c_void_p]),
     "vissm_profile_enable": (None, [_i32]),

@@ -153,7 +153,15 @@ def handle_opts(argv=None):
                              "the GPU, each with a fully adapted particle filter of N particles (64 .. 1024, a power of "
                              "two), started at posterior theta samples, and write the draws of p(theta | y) after the "
                              "default burn-in, their quantiles beside q(theta)'s and the split-R-hat to this .npz file")
+    parser.add_argument("--mcmc-adapt", action="store_true",
+                        help="With --mcmc: every chain adapts its own proposal on the GPU over the first half of the "
+                             "iterations (robust adaptive Metropolis towards 23.4 %% acceptance) and keeps it frozen "
+                             "over the second half, which is kept; for a q(theta) much wider than the posterior, where "
+                             "the shared proposal accepts a few per mille.  Also written: the chains' final factors "
+                             "and their acceptance while adapting")
     args = parser.parse_args(argv)
+    if args.mcmc_adapt and args.mcmc is None:
+        parser.error("--mcmc-adapt applies to --mcmc: give it")
     if args.mcmc is not None:
         try:
             args.mcmc = (int(args.mcmc[0]), int(args.mcmc[1]), int(args.mcmc[2]), args.mcmc[3])

@@ -289,6 +289,19 @@ int hc_mh_accept(double logu, double ll_prop, double ll_cur, double lp_prop, dou
   return vissm::mh::accept(logu, ll_prop, ll_cur, lp_prop, lp_cur) ? 1 : 0;
 }
 
+// The adaptive chain's update (mh_math.hpp: the code pmmh_adaptive_kernel's thread 0 runs).  hc_mh_alpha: the
+// acceptance probability from the state before the decision; hc_mh_eta: the step size of the absolute iteration i;
+// hc_mh_adapt: L [P][P] -> L' in place from the normals xi [P], returns 1 when L changed, 0 when it was kept.
+double hc_mh_alpha(double ll_prop, double ll_cur, double lp_prop, double lp_cur) {
+  return vissm::mh::accept_prob(ll_prop, ll_cur, lp_prop, lp_cur);
+}
+double hc_mh_eta(int P, int64_t i, double gamma) { return vissm::mh::adapt_eta(P, i, gamma); }
+int hc_mh_adapt(float* L, const float* xi, double alpha, double eta, double target, int P) {
+  if (P < 1 || P > vissm::mh::kMaxP) return -1;
+  double work[vissm::mh::adapt_work(vissm::mh::kMaxP)];
+  return vissm::mh::adapt(L, xi, alpha, eta, target, P, work) ? 1 : 0;
+}
+
 // One iteration of one stochastic-volatility chain (sv_pmmh_kernel's, pmmh.hip) run serially on mh_math.hpp and
 // svf::filter_step: iteration i of chain c of C with n particles from the state theta [4] with the estimate ll_cur.
 // The proposal's normals come from box_muller4_ref, the filter's from the same formula on the Philox counter

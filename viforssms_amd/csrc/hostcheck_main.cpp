@@ -21,6 +21,8 @@
 // cases: the counter's second word, u inside (0, 1), a zero factor, the -inf and NaN decisions;
 // whole iterations of the stochastic-volatility chain run serially (hc_svpmmh_iteration): a zero factor proposes theta
 // itself, the traces rebuild ll', a zero in the series and a state that is not finite kill the proposal;
+// the adaptive chain's factor update (mh::adapt): updates and downdates at P = 3, 4, 5 against the rank-one identity, the
+// r2 <= 0 guard, an fp32-underflowing diagonal and xi = 0;
 // any sanitizer report aborts the run (-fno-sanitize-recover=all).
 // Exit 0 = all checks passed.  Not part of the product path.
 #include <cmath>
@@ -82,6 +84,9 @@ void hc_mh_xi(uint64_t r, uint64_t seed, float out[8]);
 void hc_mh_propose(const float* th, const float* L, const float* xi, int P, float* out);
 double hc_mh_log_prior(const float* th, const float* prior, int P);
 int hc_mh_accept(double logu, double ll_prop, double ll_cur, double lp_prop, double lp_cur);
+double hc_mh_alpha(double ll_prop, double ll_cur, double lp_prop, double lp_cur);
+double hc_mh_eta(int P, int64_t i, double gamma);
+int hc_mh_adapt(float* L, const float* xi, double alpha, double eta, double target, int P);
 int hc_svpmmh_iteration(uint64_t seed, uint64_t row0, uint64_t i, uint64_t C, uint64_t c, int n, int T, float dt,
                         const float* theta, double ll_cur, const float* L, const float* prior, float h_start,
                         const float* y, float* theta_prop, double* out, float* h_tr, uint64_t* q_tr, int32_t* anc_tr,
@@ -855,6 +860,93 @@ int check_mh() {
   return bad;
 }
 
+// mh::adapt (the adaptive chain's factor update): an update and a downdate at P = 3, 4, 5 reproduce
+// L (I + d xi xi^T / |xi|^2) L^T to the fp32 rounding of the factor and keep a positive diagonal; a downdate that
+// reaches r2 <= 0, a diagonal that underflows in fp32 and xi = 0 hand the input back untouched; alpha and eta at
+// their corners
+int check_mh_adapt() {
+  int bad = 0;
+  for (int P : {3, 4, 5}) {
+    for (double alpha : {1.0, 0.0}) {
+      std::vector<float> L(static_cast<size_t>(P) * P, 0.f), L0, xi(8);
+      for (int p = 0; p < P; ++p) {
+        for (int j = 0; j < p; ++j) L[static_cast<size_t>(p) * P + j] = static_cast<float>(uniform(-0.5, 0.5));
+        L[static_cast<size_t>(p) * P + p] = static_cast<float>(uniform(0.5, 1.5));
+      }
+      for (float& x : xi) x = static_cast<float>(uniform(-2.0, 2.0));
+      L0 = L;
+      const double eta = 0.7, d = eta * (alpha - 0.234);
+      if (hc_mh_adapt(L.data(), xi.data(), alpha, eta, 0.234, P) != 1) { std::printf("adapt: P=%d kept\n", P); ++bad; }
+      double n2 = 0.0, big = 0.0, err = 0.0;
+      std::vector<double> w(P);
+      for (int j = 0; j < P; ++j) n2 += static_cast<double>(xi[j]) * xi[j];
+      for (int p = 0; p < P; ++p) {
+        w[p] = 0.0;
+        for (int j = 0; j <= p; ++j) w[p] += static_cast<double>(L0[static_cast<size_t>(p) * P + j]) * xi[j];
+      }
+      for (int p = 0; p < P; ++p) {
+        if (!(L[static_cast<size_t>(p) * P + p] > 0.f)) { std::printf("adapt: diagonal\n"); ++bad; }
+        for (int q = 0; q < P; ++q) {
+          double got = 0.0, want = d * w[p] * w[q] / n2;
+          for (int j = 0; j < P; ++j) {
+            got += static_cast<double>(L[static_cast<size_t>(p) * P + j]) * L[static_cast<size_t>(q) * P + j];
+            want += static_cast<double>(L0[static_cast<size_t>(p) * P + j]) * L0[static_cast<size_t>(q) * P + j];
+          }
+          big = std::fmax(big, std::fabs(want));
+          err = std::fmax(err, std::fabs(got - want));
+          if (q > p && L[static_cast<size_t>(p) * P + q] != 0.f) { std::printf("adapt: upper part\n"); ++bad; }
+        }
+      }
+      if (!(err <= 1e-6 * big)) { std::printf("adapt: P=%d alpha=%g identity %g of %g\n", P, alpha, err, big); ++bad; }
+      // xi = 0: nothing to do
+      std::vector<float> zero(8, 0.f), keep = L;
+      if (hc_mh_adapt(L.data(), zero.data(), alpha, eta, 0.234, P) != 0 ||
+          std::memcmp(L.data(), keep.data(), L.size() * sizeof(float)) != 0) {
+        std::printf("adapt: xi = 0\n");
+        ++bad;
+      }
+    }
+    // a downdate with |d| > 1 along e_0 (outside the kernel's range, the guard's own case): r2 <= 0 at k = 0
+    {
+      std::vector<float> L(static_cast<size_t>(P) * P, 0.f), xi(8, 0.f);
+      for (int p = 0; p < P; ++p) L[static_cast<size_t>(p) * P + p] = 1.f;
+      xi[0] = 1.f;
+      const std::vector<float> keep = L;
+      if (hc_mh_adapt(L.data(), xi.data(), 0.0, 8.0, 0.5, P) != 0 ||
+          std::memcmp(L.data(), keep.data(), L.size() * sizeof(float)) != 0) {
+        std::printf("adapt: r2 <= 0\n");
+        ++bad;
+      }
+    }
+    // a diagonal of the smallest subnormal, quartered by the downdate: rounds to 0 in fp32
+    {
+      std::vector<float> L(static_cast<size_t>(P) * P, 0.f), xi(8, 0.f);
+      for (int p = 0; p < P; ++p) L[static_cast<size_t>(p) * P + p] = 1.f;
+      L[0] = 1.4e-45f;
+      xi[0] = 1.f;
+      const std::vector<float> keep = L;
+      if (hc_mh_adapt(L.data(), xi.data(), 0.0, 1.0, 0.9375, P) != 0 ||
+          std::memcmp(L.data(), keep.data(), L.size() * sizeof(float)) != 0) {
+        std::printf("adapt: fp32 underflow\n");
+        ++bad;
+      }
+    }
+  }
+  const double inf = INFINITY;
+  if (hc_mh_alpha(NAN, -3.0, 0.0, 0.0) != 0.0 || hc_mh_alpha(-inf, -inf, 0.0, 0.0) != 0.0 ||
+      hc_mh_alpha(-3.0, -inf, 0.0, 0.0) != 1.0 || hc_mh_alpha(-3.0, -3.0, 0.0, 0.0) != 1.0 ||
+      hc_mh_alpha(-inf, -3.0, 0.0, 0.0) != 0.0 || hc_mh_alpha(-4.0, -3.0, 0.0, 0.0) != std::exp(-1.0)) {
+    std::printf("adapt: alpha\n");
+    ++bad;
+  }
+  if (hc_mh_eta(3, 0, 0.5) != 1.0 || hc_mh_eta(3, 7, 0.5) != 1.0 || !(hc_mh_eta(3, 9, 0.5) < 1.0) ||
+      hc_mh_eta(4, 3, 1.0) != 1.0 || std::fabs(hc_mh_eta(4, 4, 1.0) - 0.8) > 1e-15) {
+    std::printf("adapt: eta\n");
+    ++bad;
+  }
+  return bad;
+}
+
 // hc_svpmmh_iteration: with a zero factor the proposal is theta itself and lp' = lp; ll' is the sum of the traced
 // increments; every traced ancestor is in range and every new state the move of its ancestor's; a chain at -inf accepts
 // a live proposal; a zero in the series, a start that is not finite and T = 0 behave as the kernel's text says
@@ -942,6 +1034,7 @@ int main() {
   bad += check_gp();
   bad += check_svf();
   bad += check_mh();
+  bad += check_mh_adapt();
   bad += check_svpmmh();
   bad += check_colkey();
   bad += check_select();

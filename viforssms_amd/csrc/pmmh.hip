@@ -371,6 +371,410 @@ __global__ __launch_bounds__(N) void sv_pmmh_kernel(uint64_t seed, uint64_t row0
   }
 }
 
+// ---- the adaptive chains (vissm_pmmh_adaptive, vissm_sv_pmmh_adaptive) ---------------------------------------------
+// pmmh_kernel and sv_pmmh_kernel with a factor per chain that follows mh::adapt (mh_math.hpp: robust adaptive
+// Metropolis) while the absolute iteration it0 + it is below adapt_end, and is frozen after: from then on the chain is
+// bit for bit the fixed-proposal chain with that factor.  The kernels are restated, not shared with the two above as
+// device functions or a template flag: those kernels' assembly stays what it was.
+//
+// The factor lives in LDS (4 P P bytes): the proposal reads it as a broadcast, thread 0 rewrites it after the decision,
+// working on a double copy that sits in LDS too (8 (P P + 2 P) bytes with v and xi; mh::adapt_work): with the copy in
+// registers the 1024-lane blocks spilled.
+// It is not kept in global memory and read back through the const __restrict__ pointer: uniform reads of such a
+// pointer go through the scalar data cache, which does not see the vector stores of the same kernel.  Two block-uniform
+// barriers per adapting iteration order the accesses: one after the proposal (every wave has read the factor; the
+// filter loop passes no barrier when no step is observed), one after the update.  Nothing of the update is live over
+// the filter loop: the normals are drawn again from their two Philox blocks (the same function, the same bits) and the
+// update's doubles live in thread 0's scope after the decision.
+// LDS per block = the twin's + 8 (P P + 2 P) + 8 ceil(P P / 2): one array of doubles, the factor's floats at its end.
+constexpr int adapt_lds_doubles(int P) { return mh::adapt_work(P) + (P * P + 1) / 2; }
+struct AdaptOut {
+  float* chol_end;
+  float* xi_trace;
+  double* alpha_trace;
+  double* eta_trace;
+  float* chol_trace;
+};
+
+// chain c's lower factor into LDS, the strict upper part 0
+template <int P>
+__device__ __forceinline__ void load_factor(float* Ls, const float* __restrict__ chol_in, size_t c, int tid) {
+  if (tid < P * P) Ls[tid] = tid % P <= tid / P ? chol_in[c * (P * P) + tid] : 0.f;
+  __syncthreads();
+}
+
+// thread 0, after the decision of entry e = c n_iter + it: the factor's update and the traces
+template <int P>
+__device__ __forceinline__ void adapt_step(float* Ls, double* Ws, uint64_t frow, uint64_t seed, bool adapting, int64_t i, double al,
+                                           double target, double gamma, const AdaptOut& a, size_t e) {
+  asm volatile("" : "+s"(frow));  // drawn again, not carried over the filter loop
+  float xi[8], v[4];
+  box_muller4(mh::words(0u, frow, seed), v);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) xi[j] = v[j];
+  box_muller4(mh::words(1u, frow, seed), v);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) xi[4 + j] = v[j];
+  double eta = 0.0;
+  if (adapting) {
+    eta = mh::adapt_eta(P, i, gamma);
+    mh::adapt(Ls, xi, al, eta, target, P, Ws);
+  }
+  if (a.xi_trace) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) a.xi_trace[e * 8 + j] = xi[j];
+  }
+  if (a.alpha_trace) a.alpha_trace[e] = al;
+  if (a.eta_trace) a.eta_trace[e] = eta;
+  if (a.chol_trace) {
+#pragma unroll
+    for (int j = 0; j < P * P; ++j) a.chol_trace[e * (P * P) + j] = Ls[j];
+  }
+}
+
+template <int MODEL, int N>
+__global__ __launch_bounds__(N) void pmmh_adaptive_kernel(uint64_t seed, uint64_t row0, int C, int n_iter, int it0, int T_total,
+                                                 float dt, float obs_std, const float* __restrict__ theta_cur,
+                                                 const double* __restrict__ ll_cur, const float* __restrict__ chol_in,
+                                                 const float* __restrict__ prior, const float* __restrict__ x_start,
+                                                 const float* __restrict__ obs, const float* __restrict__ obs_bin,
+                                                 int adapt_end, double target, double gamma, Out o, AdaptOut a) {
+  constexpr int S = VISSM_MODEL_S(MODEL), P = VISSM_MODEL_P(MODEL);
+  constexpr int NW = N / 64, LOG2N = pf::log2_of(N);
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const size_t c = blockIdx.x;
+
+  __shared__ uint64_t Cs[N];
+  __shared__ float xs[S * N];
+  __shared__ float wmax[16];
+  __shared__ uint64_t wtot[16];
+  __shared__ double Ws[adapt_lds_doubles(P)];  // the update's doubles, then the factor
+  float* const Ls = reinterpret_cast<float*>(Ws + mh::adapt_work(P));
+
+  // the chain's state and the launch's constants: block-uniform
+  float th[mh::kMaxP] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  float x0[S];
+#pragma unroll
+  for (int i = 0; i < P; ++i) th[i] = theta_cur[c * P + i];
+#pragma unroll
+  for (int d = 0; d < S; ++d) x0[d] = x_start[d];
+  double ll = ll_cur[c];
+  double lp = uni(mh::log_prior(th, prior, P));
+  const uint32_t k0 = static_cast<uint32_t>(seed), k1 = static_cast<uint32_t>(seed >> 32);
+  load_factor<P>(Ls, chol_in, c, tid);
+  const bool traced = a.xi_trace || a.alpha_trace || a.eta_trace || a.chol_trace;
+  const float R = obs_std * obs_std;
+
+  for (int it = 0; it < n_iter; ++it) {
+    const uint64_t frow = mh::row_of(row0, static_cast<uint64_t>(it0) + it, C, c, N);
+
+    // block-uniform: the absolute iteration is below adapt_end
+    const bool adapting = static_cast<int64_t>(it0) + it < adapt_end;
+    // the prior is read again in every iteration (scalar loads), as pmmh_kernel reads it; the factor is the
+    // chain's own, in LDS: every thread reads the same words
+    const float* pr = prior;
+    asm volatile("" : "+s"(pr));
+
+    // the proposal
+    float thp[mh::kMaxP] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    {
+      float xi[8], v[4];
+      box_muller4(mh::words(0u, frow, seed), v);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) xi[i] = v[i];
+      box_muller4(mh::words(1u, frow, seed), v);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) xi[4 + i] = v[i];
+      mh::propose(th, Ls, xi, P, thp);
+#pragma unroll
+      for (int i = 0; i < P; ++i) thp[i] = uni(thp[i]);
+    }
+    // every wave has read the factor before thread 0 rewrites it (the filter loop below may pass no barrier)
+    if (adapting) __syncthreads();
+
+    // the fully adapted filter at theta' over steps 0 .. T_total - 1
+    const sim::Par par = sim::prepare<MODEL>(thp, dt);
+    float x[sim::kMaxS] = {0.f, 0.f};
+#pragma unroll
+    for (int d = 0; d < S; ++d) x[d] = x0[d];
+    sim::start<MODEL>(x);
+    double llp = 0.0;
+    const uint64_t row = frow + static_cast<uint64_t>(tid);
+    uint32_t j = 0u, g = 0u;  // stream entry of the step's first normal and its Philox group
+    float cur[4], nxt[4];
+    draw4(g, row, k0, k1, cur);
+    draw4(g + 1, row, k0, k1, nxt);
+
+    for (int ta = 0; ta < T_total; ++ta) {
+      const uint32_t qd = j & 3u;
+      float n[2];
+      if constexpr (S == 2) {
+        n[0] = qd ? cur[2] : cur[0];
+        n[1] = qd ? cur[3] : cur[1];
+      } else {
+        n[0] = qd == 0 ? cur[0] : qd == 1 ? cur[1] : qd == 2 ? cur[2] : cur[3];
+        n[1] = 0.f;
+      }
+      // every thread reads the same addresses: block-uniform
+      float yv[S], bv[S];
+      bool observed = false;
+#pragma unroll
+      for (int d = 0; d < S; ++d) {
+        bv[d] = obs_bin[static_cast<size_t>(d) * T_total + ta];
+        yv[d] = obs[static_cast<size_t>(d) * T_total + ta];
+        observed = observed || bv[d] != 0.f;
+      }
+      if (!observed) {
+        sim::advance<MODEL>(x, par, n, 0.f, nullptr);
+      } else {
+        const bool ok = sim::alive(MODEL, x);
+        const float lw = ok ? gp::state_logw<MODEL>(x, par, yv, bv, R) : -INFINITY;
+        const float wm = wave_max(lw);
+        if (lane == 0) wmax[wid] = wm;
+#pragma unroll
+        for (int d = 0; d < S; ++d) xs[d * N + tid] = x[d];
+        __syncthreads();  // A
+        float m = wmax[0];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) m = fmaxf(m, wmax[w]);
+        m = uni(m);  // the same LDS words in every thread
+        const uint64_t q = pf::quantise(lw, m, ok);
+        const uint64_t cs = wave_scan(q, lane);
+        if (lane == 63) wtot[wid] = cs;
+        __syncthreads();  // B
+        uint64_t before = 0, W = 0;
+#pragma unroll 2
+        for (int w = 0; w < NW; ++w) {
+          if (w < wid) before += wtot[w];
+          W += wtot[w];
+        }
+        Cs[tid] = cs + before;
+        W = uni(W);  // block-uniform: the branches below are scalar
+        __syncthreads();  // C
+        if (W > 0) {
+          const uint32_t U = pf::resample_u(seed, static_cast<uint32_t>(ta), frow);
+          int anc = pf::ancestor(Cs, N, pf::threshold(static_cast<uint32_t>(tid), U, W, LOG2N));
+          anc = min(anc, N - 1);  // tau < W = C[N - 1]: never taken
+#pragma unroll
+          for (int d = 0; d < S; ++d) x[d] = xs[d * N + anc];
+          gp::advance<MODEL>(x, par, yv, bv, R, n);
+          llp = uni(llp + pf::ll_increment(m, W, N));
+        } else {  // no live particle with a weight: the proposal is dead
+          llp = -INFINITY;
+        }
+        __syncthreads();  // D: the gather is over before the next observed step overwrites the staging arrays
+        if (W == 0) break;
+      }
+      j += S;
+      if ((j & 3u) == 0u) {  // uniform: the next step opens a new group; draw the one after it now
+#pragma unroll
+        for (int i = 0; i < 4; ++i) cur[i] = nxt[i];
+        ++g;
+        draw4(g + 1, row, k0, k1, nxt);
+      }
+    }
+
+    // the decision (its uniform and the proposal's prior are not needed before: they are not kept over the filter)
+    const double lpp = mh::log_prior(thp, pr, P);
+    const double logu = mh::log_uniform(mh::words(2u, frow, seed).x);
+    // the acceptance probability, from the state before the decision
+    double al = 0.0;
+    if (adapting || traced) al = uni(mh::accept_prob(llp, ll, lpp, lp));
+    const bool acc = __builtin_amdgcn_readfirstlane(mh::accept(logu, llp, ll, lpp, lp) ? 1 : 0) != 0;
+    if (acc) {
+#pragma unroll
+      for (int i = 0; i < P; ++i) th[i] = thp[i];
+      ll = uni(llp);
+      lp = uni(lpp);
+    }
+    if (tid == 0) {
+      const size_t e = c * static_cast<size_t>(n_iter) + it;
+#pragma unroll
+      for (int i = 0; i < P; ++i) o.theta_chain[e * P + i] = th[i];
+      o.ll_chain[e] = ll;
+      o.accept[e] = acc ? 1 : 0;
+      if (o.theta_prop) {
+#pragma unroll
+        for (int i = 0; i < P; ++i) o.theta_prop[e * P + i] = thp[i];
+      }
+      if (o.ll_prop) o.ll_prop[e] = llp;
+      if (o.logu) o.logu[e] = logu;
+      // the update, in a scope of its own: nothing of it is live over the filter loop
+      if (adapting || traced)
+        adapt_step<P>(Ls, Ws, frow, seed, adapting, static_cast<int64_t>(it0) + it, al, target, gamma, a, e);
+    }
+    // thread 0's factor is in LDS before the next iteration's proposal reads it
+    if (adapting) __syncthreads();
+  }
+  if (tid == 0) {
+#pragma unroll
+    for (int i = 0; i < P; ++i) o.theta_end[c * P + i] = th[i];
+    o.ll_end[c] = ll;
+#pragma unroll
+    for (int i = 0; i < P * P; ++i) a.chol_end[c * (P * P) + i] = Ls[i];
+  }
+}
+
+
+template <int N>
+__global__ __launch_bounds__(N) void sv_pmmh_adaptive_kernel(uint64_t seed, uint64_t row0, int C, int n_iter, int it0,
+                                                    int T_total, float dt, const float* __restrict__ theta_cur,
+                                                    const double* __restrict__ ll_cur,
+                                                    const float* __restrict__ chol_in,
+                                                    const float* __restrict__ prior, const float* __restrict__ h_start,
+                                                    const float* __restrict__ obs, int adapt_end, double target,
+                                                    double gamma, Out o, AdaptOut a) {
+  constexpr int P = kSvP;
+  constexpr int NW = N / 64, LOG2N = pf::log2_of(N);
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const size_t c = blockIdx.x;
+
+  __shared__ uint64_t Cs[N];
+  __shared__ float xs[N];
+  __shared__ float wmax[16];
+  __shared__ uint64_t wtot[16];
+  __shared__ double Ws[adapt_lds_doubles(P)];  // the update's doubles, then the factor
+  float* const Ls = reinterpret_cast<float*>(Ws + mh::adapt_work(P));
+
+  // the chain's state and the launch's constants: block-uniform
+  float th[mh::kMaxP] = {0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int i = 0; i < P; ++i) th[i] = theta_cur[c * P + i];
+  float h0 = h_start[0];
+  if (!__builtin_isfinite(h0)) h0 = sim::quiet_nan();
+  double ll = ll_cur[c];
+  double lp = uni(mh::log_prior(th, prior, P));
+  const uint32_t k0 = static_cast<uint32_t>(seed), k1 = static_cast<uint32_t>(seed >> 32);
+  load_factor<P>(Ls, chol_in, c, tid);
+  const bool traced = a.xi_trace || a.alpha_trace || a.eta_trace || a.chol_trace;
+
+  for (int it = 0; it < n_iter; ++it) {
+    const uint64_t frow = mh::row_of(row0, static_cast<uint64_t>(it0) + it, C, c, N);
+
+    // block-uniform: the absolute iteration is below adapt_end
+    const bool adapting = static_cast<int64_t>(it0) + it < adapt_end;
+    // the prior is read again in every iteration (scalar loads), as pmmh_kernel reads it; the factor is the
+    // chain's own, in LDS: every thread reads the same words
+    const float* pr = prior;
+    asm volatile("" : "+s"(pr));
+
+    // the proposal
+    float thp[mh::kMaxP] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    {
+      float xi[8], v[4];
+      box_muller4(mh::words(0u, frow, seed), v);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) xi[i] = v[i];
+      box_muller4(mh::words(1u, frow, seed), v);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) xi[4 + i] = v[i];
+      mh::propose(th, Ls, xi, P, thp);
+#pragma unroll
+      for (int i = 0; i < P; ++i) thp[i] = uni(thp[i]);
+    }
+    // every wave has read the factor before thread 0 rewrites it (the filter loop below may pass no barrier)
+    if (adapting) __syncthreads();
+
+    // the filter at theta' over steps 0 .. T_total - 1
+    const sim::Par par = sim::prepare<VISSM_MODEL_SV>(thp, dt);
+    float h = h0;
+    double llp = 0.0;
+    const uint64_t row = frow + static_cast<uint64_t>(tid);
+    uint32_t j = 0u, g = 0u;  // stream entry of the step's normal and its Philox group
+    float cur[4], nxt[4];
+    draw4(g, row, k0, k1, cur);
+    draw4(g + 1, row, k0, k1, nxt);
+
+    for (int ta = 0; ta < T_total; ++ta) {
+      const uint32_t qd = j & 3u;
+      const float n = qd == 0 ? cur[0] : qd == 1 ? cur[1] : qd == 2 ? cur[2] : cur[3];
+      // every thread reads the same addresses: block-uniform
+      const svf::Obs ob = svf::obs_prep(obs[ta], obs[static_cast<size_t>(ta) + 1], par);
+      const bool ok = __builtin_isfinite(h);
+      const float lw = svf::state_logw(h, ob);
+      const float wm = wave_max(lw);
+      if (lane == 0) wmax[wid] = wm;
+      xs[tid] = h;
+      __syncthreads();  // A
+      float m = wmax[0];
+#pragma unroll
+      for (int w = 1; w < NW; ++w) m = fmaxf(m, wmax[w]);
+      m = uni(m);  // the same LDS words in every thread
+      const uint64_t q = pf::quantise(lw, m, ok);
+      const uint64_t cs = wave_scan(q, lane);
+      if (lane == 63) wtot[wid] = cs;
+      __syncthreads();  // B
+      uint64_t before = 0, W = 0;
+#pragma unroll 2
+      for (int w = 0; w < NW; ++w) {
+        if (w < wid) before += wtot[w];
+        W += wtot[w];
+      }
+      Cs[tid] = cs + before;
+      W = uni(W);  // block-uniform: the branches below are scalar
+      __syncthreads();  // C
+      if (W > 0) {
+        const uint32_t U = pf::resample_u(seed, static_cast<uint32_t>(ta), frow);
+        int anc = pf::ancestor(Cs, N, pf::threshold(static_cast<uint32_t>(tid), U, W, LOG2N));
+        anc = min(anc, N - 1);  // tau < W = C[N - 1]: never taken
+        h = svf::move(xs[anc], par, n);
+        llp = uni(llp + pf::ll_increment(m, W, N));
+      } else {  // no live particle with a weight (a zero in y gives NaN weights): the proposal is dead
+        llp = -INFINITY;
+      }
+      __syncthreads();  // D: the gather is over before the next step overwrites the staging arrays
+      if (W == 0) break;
+      ++j;
+      if ((j & 3u) == 0u) {  // uniform: the next step opens a new group; draw the one after it now
+#pragma unroll
+        for (int i = 0; i < 4; ++i) cur[i] = nxt[i];
+        ++g;
+        draw4(g + 1, row, k0, k1, nxt);
+      }
+    }
+
+    // the decision
+    const double lpp = mh::log_prior(thp, pr, P);
+    const double logu = mh::log_uniform(mh::words(2u, frow, seed).x);
+    // the acceptance probability, from the state before the decision
+    double al = 0.0;
+    if (adapting || traced) al = uni(mh::accept_prob(llp, ll, lpp, lp));
+    const bool acc = __builtin_amdgcn_readfirstlane(mh::accept(logu, llp, ll, lpp, lp) ? 1 : 0) != 0;
+    if (acc) {
+#pragma unroll
+      for (int i = 0; i < P; ++i) th[i] = thp[i];
+      ll = uni(llp);
+      lp = uni(lpp);
+    }
+    if (tid == 0) {
+      const size_t e = c * static_cast<size_t>(n_iter) + it;
+#pragma unroll
+      for (int i = 0; i < P; ++i) o.theta_chain[e * P + i] = th[i];
+      o.ll_chain[e] = ll;
+      o.accept[e] = acc ? 1 : 0;
+      if (o.theta_prop) {
+#pragma unroll
+        for (int i = 0; i < P; ++i) o.theta_prop[e * P + i] = thp[i];
+      }
+      if (o.ll_prop) o.ll_prop[e] = llp;
+      if (o.logu) o.logu[e] = logu;
+      // the update, in a scope of its own: nothing of it is live over the filter loop
+      if (adapting || traced)
+        adapt_step<P>(Ls, Ws, frow, seed, adapting, static_cast<int64_t>(it0) + it, al, target, gamma, a, e);
+    }
+    // thread 0's factor is in LDS before the next iteration's proposal reads it
+    if (adapting) __syncthreads();
+  }
+  if (tid == 0) {
+#pragma unroll
+    for (int i = 0; i < P; ++i) o.theta_end[c * P + i] = th[i];
+    o.ll_end[c] = ll;
+#pragma unroll
+    for (int i = 0; i < P * P; ++i) a.chol_end[c * (P * P) + i] = Ls[i];
+  }
+}
+
+
 // the checks the two entries share, with the entry's name in the message
 int check_chain_args(const char* name, const VissmPmmhDesc* d, bool pointers, bool pointers_iter, bool pointers_t) {
   VISSM_CHECK_ARG(pf::valid_n(d->N), "%s: N=%d particles (64, 128, 256, 512 or 1024)", name, d->N);
@@ -454,5 +858,96 @@ extern "C" int vissm_sv_pmmh(const VissmPmmhDesc* d, uint64_t seed, uint64_t row
                        o);
   });
   VISSM_CHECK_LAUNCH("sv_pmmh");
+  return VISSM_OK;
+}
+
+// the checks the two adaptive entries add
+static int check_adapt_args(const char* name, int32_t adapt_end, double target_accept, double gamma, const void* chol_in,
+                            const void* chol_end) {
+  VISSM_CHECK_ARG(adapt_end >= 0, "%s: adapt_end=%d (an absolute iteration, at least 0)", name, adapt_end);
+  // (a NaN fails either comparison)
+  VISSM_CHECK_ARG(target_accept > 0.0 && target_accept < 1.0, "%s: target_accept=%g outside (0, 1)", name,
+                  target_accept);
+  VISSM_CHECK_ARG(gamma > 0.0 && gamma <= 1.0, "%s: gamma=%g outside (0, 1]", name, gamma);
+  VISSM_CHECK_ARG(chol_in && chol_end, "%s: null pointer (chol_in, chol_end)", name);
+  return VISSM_OK;
+}
+
+// the twin's + 8 (P P + 2 P) (the update's doubles) + 8 ceil(P P / 2) (the chain's factor)
+extern "C" int32_t vissm_pmmh_adaptive_lds_bytes(int32_t model, int32_t N) {
+  const int32_t twin = vissm_pmmh_lds_bytes(model, N);
+  const int P = twin ? VISSM_MODEL_P(model) : 0;
+  return twin ? twin + 8 * adapt_lds_doubles(P) : 0;
+}
+
+extern "C" int vissm_pmmh_adaptive(const VissmPmmhDesc* d, uint64_t seed, uint64_t row0, const float* theta_cur,
+                                   const double* ll_cur, const float* chol_in, const float* prior,
+                                   const float* x_start, const float* obs, const float* obs_bin, int32_t adapt_end,
+                                   double target_accept, double gamma, float* theta_chain, double* ll_chain,
+                                   int32_t* accept, float* theta_end, double* ll_end, float* chol_end,
+                                   float* theta_prop, double* ll_prop, double* logu, float* xi_trace,
+                                   double* alpha_trace, double* eta_trace, float* chol_trace, void* stream) {
+  // host arithmetic only, before any GPU call
+  VISSM_CHECK_ARG(d, "pmmh_adaptive: null descriptor");
+  VISSM_CHECK_ARG(d->model != VISSM_MODEL_SV,
+                  "pmmh_adaptive: no observation model for SV (its first coordinate is the observed series)");
+  VISSM_CHECK_ARG(d->model == VISSM_MODEL_AR || d->model == VISSM_MODEL_LV || d->model == VISSM_MODEL_FHN,
+                  "pmmh_adaptive: unknown model %d", d->model);
+  if (const int rc = check_chain_args("pmmh_adaptive", d, theta_cur && ll_cur && prior && x_start && theta_end && ll_end,
+                                      theta_chain && ll_chain && accept, obs && obs_bin))
+    return rc;
+  if (const int rc = check_adapt_args("pmmh_adaptive", adapt_end, target_accept, gamma, chol_in, chol_end)) return rc;
+  VISSM_CHECK_ARG(d->T_total >= 0, "pmmh_adaptive: T_total=%d", d->T_total);
+  const int S = VISSM_MODEL_S(d->model);
+  VISSM_CHECK_ARG(static_cast<int64_t>(d->T_total) * S < (int64_t{1} << 31),
+                  "pmmh_adaptive: T_total S = %d %d reaches 2^31", d->T_total, S);
+  VISSM_CHECK_ARG(d->obs_std > 0.f && d->obs_std <= 3.4028234e38f,
+                  "pmmh_adaptive: a positive, finite obs_std expected, got %g", static_cast<double>(d->obs_std));
+  const Out o{theta_chain, ll_chain, accept, theta_end, ll_end, theta_prop, ll_prop, logu};
+  const AdaptOut a{chol_end, xi_trace, alpha_trace, eta_trace, chol_trace};
+  dispatch_model(d->model, [&](auto model) {
+    dispatch_n(d->N, [&](auto n) {
+      hipLaunchKernelGGL((pmmh_adaptive_kernel<decltype(model)::value, decltype(n)::value>), dim3(d->C), dim3(d->N), 0,
+                         as_stream(stream), seed, row0, d->C, d->n_iter, d->it0, d->T_total, d->dt, d->obs_std,
+                         theta_cur, ll_cur, chol_in, prior, x_start, obs, obs_bin, adapt_end, target_accept, gamma, o,
+                         a);
+    });
+  });
+  VISSM_CHECK_LAUNCH("pmmh_adaptive");
+  return VISSM_OK;
+}
+
+// the twin's + 8 (P P + 2 P) + 8 ceil(P P / 2), P = 4
+extern "C" int32_t vissm_sv_pmmh_adaptive_lds_bytes(int32_t N) {
+  const int32_t twin = vissm_sv_pmmh_lds_bytes(N);
+  return twin ? twin + 8 * adapt_lds_doubles(kSvP) : 0;
+}
+
+extern "C" int vissm_sv_pmmh_adaptive(const VissmPmmhDesc* d, uint64_t seed, uint64_t row0, const float* theta_cur,
+                                      const double* ll_cur, const float* chol_in, const float* prior,
+                                      const float* h_start, const float* obs, int32_t adapt_end, double target_accept,
+                                      double gamma, float* theta_chain, double* ll_chain, int32_t* accept,
+                                      float* theta_end, double* ll_end, float* chol_end, float* theta_prop,
+                                      double* ll_prop, double* logu, float* xi_trace, double* alpha_trace,
+                                      double* eta_trace, float* chol_trace, void* stream) {
+  // host arithmetic only, before any GPU call
+  VISSM_CHECK_ARG(d, "sv_pmmh_adaptive: null descriptor");
+  VISSM_CHECK_ARG(d->model == VISSM_MODEL_SV, "sv_pmmh_adaptive: model %d is not SV (vissm_pmmh_adaptive has the others)",
+                  d->model);
+  if (const int rc = check_chain_args("sv_pmmh_adaptive", d, theta_cur && ll_cur && prior && h_start && theta_end && ll_end,
+                                      theta_chain && ll_chain && accept, obs != nullptr))
+    return rc;
+  if (const int rc = check_adapt_args("sv_pmmh_adaptive", adapt_end, target_accept, gamma, chol_in, chol_end)) return rc;
+  VISSM_CHECK_ARG(d->T_total >= 0 && d->T_total < 2147483647, "sv_pmmh_adaptive: T_total=%d", d->T_total);
+  VISSM_CHECK_ARG(d->dt > 0.f && d->dt <= 3.4028234e38f, "sv_pmmh_adaptive: dt must be positive and finite, got %g",
+                  static_cast<double>(d->dt));
+  const Out o{theta_chain, ll_chain, accept, theta_end, ll_end, theta_prop, ll_prop, logu};
+  const AdaptOut a{chol_end, xi_trace, alpha_trace, eta_trace, chol_trace};
+  dispatch_n(d->N, [&](auto n) {
+    hipLaunchKernelGGL((sv_pmmh_adaptive_kernel<decltype(n)::value>), dim3(d->C), dim3(d->N), 0, as_stream(stream), seed,
+                       row0, d->C, d->n_iter, d->it0, d->T_total, d->dt, theta_cur, ll_cur, chol_in, prior, h_start, obs,
+                       adapt_end, target_accept, gamma, o, a);
+  });
+  VISSM_CHECK_LAUNCH("sv_pmmh_adaptive");
   return VISSM_OK;
 }

@@ -285,7 +285,8 @@ class PosteriorDiagnostics:
     # ------------------------------------------------------------------ the theta posterior by PMMH
     @torch.no_grad()
     def theta_mcmc(self, n_chains: int = 64, n_particles: int = 256, n_iter: int = 2000, burn_in: int = 500,
-                   step_scale: float = 1.0, probs=DEFAULT_PROBS) -> Dict[str, np.ndarray]:
+                   step_scale: float = 1.0, probs=DEFAULT_PROBS, adapt: bool = False, target_accept: float = 0.234,
+                   adapt_decay: float = 0.5) -> Dict[str, np.ndarray]:
         """The posterior p(theta | y) to lay over q(theta): C = n_chains particle marginal Metropolis-Hastings chains
         (ops.pmmh; Andrieu, Doucet & Holenstein 2010) whose acceptance ratio holds the fully adapted filter's unbiased
         estimate of p(y | theta) from N = n_particles particles, so they target p(theta | y) exactly for any N.  The
@@ -304,12 +305,24 @@ class PosteriorDiagnostics:
         mcmc/{mean, sd} [P] and mcmc/quantiles [Q, P] summarise the pooled draws on theta/quantiles' scale
         (log-parameters exponentiated) at the same probs and by the same estimator, with theta/{mean, sd, quantiles}
         of q(theta) copied in beside them; mcmc/rhat [P] is the split-R-hat of the raw draws; mcmc/prop_chol [P, P].
-        SV has no observation model: ValueError (volatility_mcmc() is SV's)."""
+        SV has no observation model: ValueError (volatility_mcmc() is SV's).
+
+        adapt = True: one fixed factor shared by all chains mixes badly when q(theta) is much wider than the posterior
+        in some coordinate (a few per mille accepted).  Then every chain starts from that factor and adapts its own
+        over the iterations [0, burn_in) inside the kernel (ops.pmmh_adaptive: robust adaptive Metropolis, a rank-one
+        update of the factor after every decision, steered to the acceptance rate target_accept with step sizes
+        min(1, P (i + 1)^-adapt_decay)), and keeps it frozen after: the kept draws come from an ordinary fixed-proposal
+        chain, which targets p(theta | y) exactly.  The launches are cut as before and chained through chol_end as
+        well.  The result gains mcmc/prop_chol_end [C, P, P], the chains' frozen factors, and mcmc/accept_rate_adapt
+        [C], the acceptance over the adaptation; mcmc/prop_chol stays the starting factor.  burn_in = 0,
+        target_accept outside (0, 1) or adapt_decay outside (0, 1]: ValueError.  With adapt = False nothing changes."""
         from . import ops
         md = self.mdef
         if md.model_id == _lib.MODEL_SV or getattr(self, "filter_data", None) is None:
             raise ValueError("theta_mcmc: SV has no observation model (its first coordinate is the observed series)")
         C, N, n_iter, burn, p = self._mcmc_args("theta_mcmc", n_chains, n_particles, n_iter, burn_in, step_scale, probs)
+        if adapt:
+            target_accept, adapt_decay = self._mcmc_adapt_args("theta_mcmc", burn, target_accept, adapt_decay)
         dev = self.engine.device
         P = _lib.MODEL_P[md.model_id]
         obs_h, bin_h, x0_h = self.filter_data
@@ -325,12 +338,19 @@ class PosteriorDiagnostics:
                                  proposal="adapted").loglik
         per = max(1, MCMC_LAUNCH_STEPS // max(T, 1))
         runs = []
+        Lc = L.repeat(C, 1, 1) if adapt else None
         for it0 in range(0, n_iter, per):
-            r = ops.pmmh(md.model_id, th, ll, L, prior, x0, obs, obs_bin, md.dt, md.obs_std, N,
-                         min(per, n_iter - it0), seed, row0 + C * N, it0=it0)
+            if adapt:
+                r = ops.pmmh_adaptive(md.model_id, th, ll, Lc, prior, x0, obs, obs_bin, md.dt, md.obs_std, N,
+                                      min(per, n_iter - it0), seed, row0 + C * N, burn, target_accept, adapt_decay,
+                                      it0=it0)
+                Lc = r.chol_end
+            else:
+                r = ops.pmmh(md.model_id, th, ll, L, prior, x0, obs, obs_bin, md.dt, md.obs_std, N,
+                             min(per, n_iter - it0), seed, row0 + C * N, it0=it0)
             th, ll = r.theta_end, r.ll_end
             runs.append(r)
-        return self._mcmc_result(runs, burn, p, probs, chol, draw)
+        return self._mcmc_result(runs, burn, p, probs, chol, draw, Lc)
 
     def _mcmc_args(self, what, n_chains, n_particles, n_iter, burn_in, step_scale, probs):
         """The checks theta_mcmc() and volatility_mcmc() share: (C, N, n_iter, burn, p)."""
@@ -344,6 +364,18 @@ class PosteriorDiagnostics:
         if not 0.0 < float(step_scale) < float("inf"):
             raise ValueError(f"{what}: step_scale={step_scale} must be positive and finite")
         return C, N, n_iter, burn, _check_probs(probs)
+
+    @staticmethod
+    def _mcmc_adapt_args(what, burn, target_accept, adapt_decay):
+        """The checks adapt = True adds: (target_accept, adapt_decay)."""
+        target_accept, adapt_decay = float(target_accept), float(adapt_decay)
+        if burn < 1:
+            raise ValueError(f"{what}: adapt=True adapts over the iterations [0, burn_in): burn_in={burn} leaves none")
+        if not 0.0 < target_accept < 1.0:
+            raise ValueError(f"{what}: target_accept={target_accept} outside (0, 1)")
+        if not 0.0 < adapt_decay <= 1.0:
+            raise ValueError(f"{what}: adapt_decay={adapt_decay} outside (0, 1]")
+        return target_accept, adapt_decay
 
     def _mcmc_walk(self, what, P, step_scale):
         """The raw theta draw posterior_summary uses (rank 0's rows, broadcast), the factor of the random walk's
@@ -367,8 +399,9 @@ class PosteriorDiagnostics:
         prior = torch.as_tensor(np.asarray(self.mdef.priors, dtype=np.float32).reshape(P, 2), device=dev)
         return draw, chol, L, prior
 
-    def _mcmc_result(self, runs, burn, p, probs, chol, draw) -> Dict[str, np.ndarray]:
-        """The result of theta_mcmc() / volatility_mcmc() from the chained launches' PmmhResults."""
+    def _mcmc_result(self, runs, burn, p, probs, chol, draw, chol_end=None) -> Dict[str, np.ndarray]:
+        """The result of theta_mcmc() / volatility_mcmc() from the chained launches' PmmhResults; chol_end: the
+        adaptive chains' frozen factors (adapt = True), which adds mcmc/prop_chol_end and mcmc/accept_rate_adapt."""
         md, dev = self.mdef, self.engine.device
         P = _lib.MODEL_P[md.model_id]
         kept = torch.cat([r.theta_chain for r in runs], 1)[:, burn:].contiguous()
@@ -377,6 +410,9 @@ class PosteriorDiagnostics:
                                       "mcmc/accept_rate": torch.cat([r.accept for r in runs], 1)[:, burn:].double()
                                       .mean(1).cpu().numpy(),
                                       "mcmc/prop_chol": chol}
+        if chol_end is not None:
+            res["mcmc/prop_chol_end"] = chol_end.cpu().numpy()
+            res["mcmc/accept_rate_adapt"] = torch.cat([r.accept for r in runs], 1)[:, :burn].double().mean(1).cpu().numpy()
         pooled = kept.view(-1, P)
         pos = list(md.theta_pos)
         if any(pos):
@@ -394,21 +430,25 @@ class PosteriorDiagnostics:
         return res
 
     def save_theta_mcmc(self, PATH: str, n_chains: int = 64, n_particles: int = 256, n_iter: int = 2000,
-                        burn_in: int = 500, step_scale: float = 1.0, probs=DEFAULT_PROBS) -> Dict[str, np.ndarray]:
+                        burn_in: int = 500, step_scale: float = 1.0, probs=DEFAULT_PROBS, adapt: bool = False,
+                        target_accept: float = 0.234, adapt_decay: float = 0.5) -> Dict[str, np.ndarray]:
         """theta_mcmc written as one .npz by rank 0 (every rank computes the same result)."""
-        return self._save_npz(PATH, self.theta_mcmc(n_chains, n_particles, n_iter, burn_in, step_scale, probs))
+        return self._save_npz(PATH, self.theta_mcmc(n_chains, n_particles, n_iter, burn_in, step_scale, probs, adapt,
+                                                    target_accept, adapt_decay))
 
     # ------------------------------------------------------------------ the theta posterior of the SV family
     @torch.no_grad()
     def volatility_mcmc(self, n_chains: int = 64, n_particles: int = 256, n_iter: int = 2000, burn_in: int = 500,
-                        step_scale: float = 1.0, probs=DEFAULT_PROBS) -> Dict[str, np.ndarray]:
+                        step_scale: float = 1.0, probs=DEFAULT_PROBS, adapt: bool = False,
+                        target_accept: float = 0.234, adapt_decay: float = 0.5) -> Dict[str, np.ndarray]:
         """theta_mcmc() for the SV family, which theta_mcmc() refuses: the same chains (ops.sv_pmmh) around
         volatility_filter()'s filter, which is exactly fully adapted.  The data and its refusals are that method's: the
         observed series y[0 .. T], every particle started at x0; ValueError for a family other than SV, a y[0 .. T]
         that is not finite, a y[0 .. T - 1] equal to 0.  The prior, the random walk's covariance step_scale^2 (2.38^2 /
         4) Sigma_q, the start at samples 0 .. C - 1 of the broadcast draw, the Philox key seed ^ MCMC_SEED_XOR, the rows
         based at global_step C N (n_iter + 1) (the initial estimates, ops.sv_filter(cloud=False), take the first C N),
-        the launches of max(1, MCMC_LAUNCH_STEPS // T) iterations and every returned key are theta_mcmc()'s."""
+        the launches of max(1, MCMC_LAUNCH_STEPS // T) iterations and every returned key are theta_mcmc()'s, and so
+        are adapt, target_accept and adapt_decay (ops.sv_pmmh_adaptive) with the two keys they add."""
         from . import ops
         md = self.mdef
         if md.model_id != _lib.MODEL_SV:
@@ -416,6 +456,8 @@ class PosteriorDiagnostics:
                              "check; this one is SV's")
         C, N, n_iter, burn, p = self._mcmc_args("volatility_mcmc", n_chains, n_particles, n_iter, burn_in, step_scale,
                                                 probs)
+        if adapt:
+            target_accept, adapt_decay = self._mcmc_adapt_args("volatility_mcmc", burn, target_accept, adapt_decay)
         y_h, T = self._volatility_series("volatility_mcmc")
         dev = self.engine.device
         P = _lib.MODEL_P[md.model_id]
@@ -428,16 +470,25 @@ class PosteriorDiagnostics:
         ll = ops.sv_filter(th, h0, obs, md.dt, N, seed, row0, cloud=False).loglik
         per = max(1, MCMC_LAUNCH_STEPS // max(T, 1))
         runs = []
+        Lc = L.repeat(C, 1, 1) if adapt else None
         for it0 in range(0, n_iter, per):
-            r = ops.sv_pmmh(th, ll, L, prior, h0, obs, md.dt, N, min(per, n_iter - it0), seed, row0 + C * N, it0=it0)
+            if adapt:
+                r = ops.sv_pmmh_adaptive(th, ll, Lc, prior, h0, obs, md.dt, N, min(per, n_iter - it0), seed,
+                                         row0 + C * N, burn, target_accept, adapt_decay, it0=it0)
+                Lc = r.chol_end
+            else:
+                r = ops.sv_pmmh(th, ll, L, prior, h0, obs, md.dt, N, min(per, n_iter - it0), seed, row0 + C * N,
+                                it0=it0)
             th, ll = r.theta_end, r.ll_end
             runs.append(r)
-        return self._mcmc_result(runs, burn, p, probs, chol, draw)
+        return self._mcmc_result(runs, burn, p, probs, chol, draw, Lc)
 
     def save_volatility_mcmc(self, PATH: str, n_chains: int = 64, n_particles: int = 256, n_iter: int = 2000,
-                             burn_in: int = 500, step_scale: float = 1.0, probs=DEFAULT_PROBS) -> Dict[str, np.ndarray]:
+                             burn_in: int = 500, step_scale: float = 1.0, probs=DEFAULT_PROBS, adapt: bool = False,
+                             target_accept: float = 0.234, adapt_decay: float = 0.5) -> Dict[str, np.ndarray]:
         """volatility_mcmc written as one .npz by rank 0 (every rank computes the same result)."""
-        return self._save_npz(PATH, self.volatility_mcmc(n_chains, n_particles, n_iter, burn_in, step_scale, probs))
+        return self._save_npz(PATH, self.volatility_mcmc(n_chains, n_particles, n_iter, burn_in, step_scale, probs,
+                                                         adapt, target_accept, adapt_decay))
 
     # ------------------------------------------------------------------ particle smoother
     @torch.no_grad()

@@ -1392,3 +1392,156 @@ def sv_pmmh(theta_cur: torch.Tensor, ll_cur: torch.Tensor, prop_chol: torch.Tens
                                     ptr(theta_end), ptr(ll_end), ptr(tp), ptr(lpr), ptr(lu), _lib.stream_handle(dev)),
           "vissm_sv_pmmh")
     return PmmhResult(theta_chain, ll_chain, accept, theta_end, ll_end, tp, lpr, lu)
+
+
+# ---------------------------------------------------------------------------------------
+# adaptive particle marginal Metropolis-Hastings (each chain learns its own proposal factor)
+# ---------------------------------------------------------------------------------------
+@dataclass
+class PmmhAdaptiveResult(PmmhResult):
+    chol_end: torch.Tensor = None               # [C, P, P]: chol_in of the call that continues at it0 + n_iter
+    xi_trace: Optional[torch.Tensor] = None     # [C, n_iter, 8] the iterations' normals as the device drew them, or None
+    alpha_trace: Optional[torch.Tensor] = None  # [C, n_iter] float64 the acceptance probabilities, or None
+    eta_trace: Optional[torch.Tensor] = None    # [C, n_iter] float64 the step sizes (0 from adapt_end on), or None
+    chol_trace: Optional[torch.Tensor] = None   # [C, n_iter, P, P] the factor after each iteration, or None
+
+
+def _adaptive_args(what: str, adapt_end, target_accept, gamma) -> tuple:
+    """The refusals the adaptive entries add, by host arithmetic: (adapt_end, target_accept, gamma)."""
+    adapt_end, target_accept, gamma = int(adapt_end), float(target_accept), float(gamma)
+    if not 0 <= adapt_end < 2 ** 31:
+        raise ValueError(f"{what}: adapt_end={adapt_end} outside 0 .. 2^31 - 1 (an absolute iteration)")
+    if not 0.0 < target_accept < 1.0:
+        raise ValueError(f"{what}: target_accept={target_accept} outside (0, 1)")
+    if not 0.0 < gamma <= 1.0:
+        raise ValueError(f"{what}: gamma={gamma} outside (0, 1]")
+    return adapt_end, target_accept, gamma
+
+
+def _adaptive_outputs(C: int, n_iter: int, P: int, trace: bool, dev):
+    """The output tensors of an adaptive launch, in the C entry's order."""
+    f32, f64 = torch.float32, torch.float64
+    e = lambda *shape, dtype=f32: torch.empty(*shape, dtype=dtype, device=dev)
+    t = lambda *shape, dtype=f32: e(*shape, dtype=dtype) if trace else None
+    return [e(C, n_iter, P), e(C, n_iter, dtype=f64), e(C, n_iter, dtype=torch.int32), e(C, P), e(C, dtype=f64),
+            e(C, P, P), t(C, n_iter, P), t(C, n_iter, dtype=f64), t(C, n_iter, dtype=f64), t(C, n_iter, 8),
+            t(C, n_iter, dtype=f64), t(C, n_iter, dtype=f64), t(C, n_iter, P, P)]
+
+
+def _adaptive_result(out) -> PmmhAdaptiveResult:
+    (theta_chain, ll_chain, accept, theta_end, ll_end, chol_end, tp, lpr, lu, xi, al, eta, ct) = out
+    return PmmhAdaptiveResult(theta_chain, ll_chain, accept, theta_end, ll_end, tp, lpr, lu, chol_end, xi, al, eta, ct)
+
+
+def pmmh_adaptive(model_id: int, theta_cur: torch.Tensor, ll_cur: torch.Tensor, chol_in: torch.Tensor,
+                  prior: torch.Tensor, x_start: torch.Tensor, obs: torch.Tensor, obs_bin: torch.Tensor, dt: float,
+                  obs_std: float, N: int, n_iter: int, seed: int, row0: int, adapt_end: int,
+                  target_accept: float = 0.234, gamma: float = 0.5, it0: int = 0,
+                  trace: bool = False) -> PmmhAdaptiveResult:
+    """pmmh with a proposal factor per chain, chol_in [C, P, P] (lower; the strict upper part is ignored), that each
+    chain adapts itself while its absolute iteration is below adapt_end and keeps frozen after (vissm_pmmh_adaptive;
+    robust adaptive Metropolis, Vihola 2012): after the decision of iteration i < adapt_end the factor takes a rank-one
+    update with d = eta (alpha - target_accept), eta = min(1, P (i + 1)^-gamma), alpha the proposal's acceptance
+    probability.  Every other argument and every PmmhResult field is pmmh's; adapt_end = 0 with chol_in = the shared
+    factor tiled is pmmh, bit for bit.  chol_end [C, P, P] is the factor after the last iteration: a call with it0' =
+    it0 + n_iter, theta_cur = theta_end, ll_cur = ll_end, chol_in = chol_end and the same adapt_end, target_accept and
+    gamma continues bitwise.  trace: also pmmh's traces, the normals, alpha, eta and the factor after each
+    iteration.  AR, LV and FHN."""
+    # the refusals of the C entry, by host arithmetic before any GPU call
+    what = "pmmh_adaptive"
+    if model_id == _lib.MODEL_SV:
+        raise ValueError(f"{what}: no observation model for SV (its first coordinate is the observed series)")
+    if model_id not in _lib.MODEL_S:
+        raise ValueError(f"{what}: unknown model {model_id}")
+    S, P = _lib.MODEL_S[model_id], _lib.MODEL_P[model_id]
+    N, n_iter, it0 = int(N), int(n_iter), int(it0)
+    if N not in _lib.PF_PARTICLES:
+        raise ValueError(f"{what}: N={N} particles, one of {_lib.PF_PARTICLES} expected")
+    if not 0.0 < float(obs_std) < float("inf"):
+        raise ValueError(f"{what}: a positive, finite obs_std expected, got {obs_std}")
+    if theta_cur.dim() != 2 or theta_cur.shape[1] != P or theta_cur.shape[0] < 1:
+        raise ValueError(f"{what}: theta_cur [C >= 1, {P}] expected, got {tuple(theta_cur.shape)}")
+    C = theta_cur.shape[0]
+    if n_iter < 0 or it0 < 0 or it0 + n_iter >= 2 ** 31:
+        raise ValueError(f"{what}: bad iterations it0={it0} n_iter={n_iter}")
+    adapt_end, target_accept, gamma = _adaptive_args(what, adapt_end, target_accept, gamma)
+    if obs.dim() != 2 or obs.shape[0] != S or obs_bin.shape != obs.shape:
+        raise ValueError(f"{what}: obs and obs_bin [{S}, T] expected, got {tuple(obs.shape)} and "
+                         f"{tuple(obs_bin.shape)}")
+    T_total = obs.shape[1]
+    if T_total * S >= 2 ** 31:
+        raise ValueError(f"{what}: T S = {T_total} * {S} reaches 2^31")
+    if not 0 <= int(row0) < 2 ** 64:
+        raise ValueError(f"{what}: row0={row0} outside [0, 2^64)")
+    if chol_in.dtype != torch.float32 or tuple(chol_in.shape) != (C, P, P):
+        raise ValueError(f"{what}: fp32 chol_in {[C, P, P]} expected, got {chol_in.dtype} {tuple(chol_in.shape)}")
+    _require_gpu(theta_cur, chol_in, prior, x_start, obs, obs_bin)
+    for name, t, shape in (("theta_cur", theta_cur, (C, P)), ("prior", prior, (P, 2)), ("x_start", x_start, (S,)),
+                           ("obs", obs, (S, T_total)), ("obs_bin", obs_bin, (S, T_total))):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape:
+            raise ValueError(f"{what}: fp32 {name} {list(shape)} expected, got {t.dtype} {tuple(t.shape)}")
+    dev = theta_cur.device
+    if not ll_cur.is_cuda or ll_cur.dtype != torch.float64 or tuple(ll_cur.shape) != (C,) or \
+            not ll_cur.is_contiguous():
+        raise ValueError(f"{what}: ll_cur: a contiguous float64 GPU tensor [{C}] expected")
+    if any(t.device != dev for t in (ll_cur, chol_in, prior, x_start, obs, obs_bin)):
+        raise ValueError(f"{what}: all tensors on one device expected")
+    key, row = ctypes.c_uint64(seed & (2 ** 64 - 1)), ctypes.c_uint64(int(row0))
+    out = _adaptive_outputs(C, n_iter, P, trace, dev)
+    d = _lib.PmmhDesc(model_id, C, N, n_iter, it0, T_total, float(dt), float(obs_std))
+    check(_lib.load().vissm_pmmh_adaptive(ctypes.byref(d), key, row, ptr(theta_cur), ptr(ll_cur), ptr(chol_in),
+                                          ptr(prior), ptr(x_start), ptr(obs), ptr(obs_bin), adapt_end, target_accept,
+                                          gamma, *[ptr(t) for t in out], _lib.stream_handle(dev)),
+          "vissm_pmmh_adaptive")
+    return _adaptive_result(out)
+
+
+def sv_pmmh_adaptive(theta_cur: torch.Tensor, ll_cur: torch.Tensor, chol_in: torch.Tensor, prior: torch.Tensor,
+                     h_start: torch.Tensor, obs: torch.Tensor, dt: float, N: int, n_iter: int, seed: int, row0: int,
+                     adapt_end: int, target_accept: float = 0.234, gamma: float = 0.5, it0: int = 0,
+                     trace: bool = False) -> PmmhAdaptiveResult:
+    """pmmh_adaptive for the stochastic-volatility model: sv_pmmh with a proposal factor per chain, chol_in [C, 4, 4],
+    adapted while the absolute iteration is below adapt_end and frozen after (vissm_sv_pmmh_adaptive).  Every other
+    argument and every PmmhResult field is sv_pmmh's; the adaptation, chol_end, the chaining and the traces are
+    pmmh_adaptive's."""
+    # the refusals of the C entry, by host arithmetic before any GPU call
+    what = "sv_pmmh_adaptive"
+    P = _lib.MODEL_P[_lib.MODEL_SV]
+    N, n_iter, it0 = int(N), int(n_iter), int(it0)
+    if N not in _lib.PF_PARTICLES:
+        raise ValueError(f"{what}: N={N} particles, one of {_lib.PF_PARTICLES} expected")
+    if not 0.0 < float(dt) < float("inf"):
+        raise ValueError(f"{what}: dt must be positive and finite, got {dt}")
+    if theta_cur.dim() != 2 or theta_cur.shape[1] != P or theta_cur.shape[0] < 1:
+        raise ValueError(f"{what}: theta_cur [C >= 1, {P}] expected, got {tuple(theta_cur.shape)}")
+    C = theta_cur.shape[0]
+    if n_iter < 0 or it0 < 0 or it0 + n_iter >= 2 ** 31:
+        raise ValueError(f"{what}: bad iterations it0={it0} n_iter={n_iter}")
+    adapt_end, target_accept, gamma = _adaptive_args(what, adapt_end, target_accept, gamma)
+    if obs.dim() != 1 or obs.shape[0] < 1 or obs.dtype != torch.float32:
+        raise ValueError(f"{what}: obs: an fp32 vector y[0 .. T] expected, got {obs.dtype} {tuple(obs.shape)}")
+    T_total = obs.shape[0] - 1
+    if T_total >= 2 ** 31 - 1:
+        raise ValueError(f"{what}: T = {T_total} reaches 2^31 - 1")
+    if not 0 <= int(row0) < 2 ** 64:
+        raise ValueError(f"{what}: row0={row0} outside [0, 2^64)")
+    if chol_in.dtype != torch.float32 or tuple(chol_in.shape) != (C, P, P):
+        raise ValueError(f"{what}: fp32 chol_in {[C, P, P]} expected, got {chol_in.dtype} {tuple(chol_in.shape)}")
+    _require_gpu(theta_cur, chol_in, prior, h_start, obs)
+    for name, t, shape in (("theta_cur", theta_cur, (C, P)), ("prior", prior, (P, 2)), ("h_start", h_start, (1,))):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape:
+            raise ValueError(f"{what}: fp32 {name} {list(shape)} expected, got {t.dtype} {tuple(t.shape)}")
+    dev = theta_cur.device
+    if not ll_cur.is_cuda or ll_cur.dtype != torch.float64 or tuple(ll_cur.shape) != (C,) or \
+            not ll_cur.is_contiguous():
+        raise ValueError(f"{what}: ll_cur: a contiguous float64 GPU tensor [{C}] expected")
+    if any(t.device != dev for t in (ll_cur, chol_in, prior, h_start, obs)):
+        raise ValueError(f"{what}: all tensors on one device expected")
+    key, row = ctypes.c_uint64(seed & (2 ** 64 - 1)), ctypes.c_uint64(int(row0))
+    out = _adaptive_outputs(C, n_iter, P, trace, dev)
+    d = _lib.PmmhDesc(_lib.MODEL_SV, C, N, n_iter, it0, T_total, float(dt), 0.0)
+    check(_lib.load().vissm_sv_pmmh_adaptive(ctypes.byref(d), key, row, ptr(theta_cur), ptr(ll_cur), ptr(chol_in),
+                                             ptr(prior), ptr(h_start), ptr(obs), adapt_end, target_accept, gamma,
+                                             *[ptr(t) for t in out], _lib.stream_handle(dev)),
+          "vissm_sv_pmmh_adaptive")
+    return _adaptive_result(out)
