@@ -284,6 +284,15 @@ int vissm_elbo_fwd_grad(const VissmElboDesc* d, const VissmElboData* data, const
                         const float* g_sde, const float* g_obs, const float* g_extra, float* sde, float* obs,
                         float* extra, float* dz, float* dtheta, void* stream);
 
+/* vissm_elbo_fwd_grad with the LV / SV / FHN kernel's waves per trajectory given by the caller instead of the
+ * library's choice (its per-model default, or VISSM_ELBO_NWV): nwv waves of a block share one trajectory, each taking
+ * a contiguous range of the chunk loop.  vissm_elbo_fwd_grad is this call at the library's choice.  Refused before
+ * any launch: nwv not 1, 2 or 4; nwv > 1 for AR (its kernel has one wave per trajectory); nwv > 1 together with
+ * data->obs_list on LV / FHN (the list's post-pass needs the whole row in one wave). */
+int vissm_elbo_fwd_grad_nwv(const VissmElboDesc* d, const VissmElboData* data, const float* z, const float* theta,
+                            const float* g_sde, const float* g_obs, const float* g_extra, float* sde, float* obs,
+                            float* extra, float* dz, float* dtheta, int32_t nwv, void* stream);
+
 /* ---------------------------------------------------------------------------
  * Global-norm clip + Adamax over one flat parameter buffer:
  * tf.global_norm / tf.clip_by_global_norm (AR.py:230-232) followed by

@@ -97,6 +97,33 @@ def test_elbo_fwd_grad_checks_without_gpu():
     assert rc < 0 and b"obs_stride" in lib.vissm_last_error()
 
 
+def test_elbo_fwd_grad_nwv_checks_without_gpu():
+    """vissm_elbo_fwd_grad_nwv (the one-pass call at a given number of waves per trajectory): nwv outside 1 / 2 / 4,
+    nwv > 1 for AR and nwv > 1 with an observation list on LV / FHN are refused before any device work; B = 0 is a
+    no-op at every valid nwv."""
+    from viforssms_amd import _lib
+    lib = _lib.load()
+    fake = ctypes.c_void_p(16)   # never dereferenced: the checks run first
+    call = lambda d, data, nwv: lib.vissm_elbo_fwd_grad_nwv(ctypes.byref(d), ctypes.byref(data), fake, fake, fake,
+                                                            fake, None, fake, fake, None, fake, fake, nwv, None)
+    plain = _lib.ElboData(None, fake, fake, fake, fake, fake, None, None, 0)
+    listed = _lib.ElboData(None, fake, fake, fake, fake, fake, None, fake, 4)
+    for model in (_lib.MODEL_LV, _lib.MODEL_SV, _lib.MODEL_FHN):
+        d = _lib.ElboDesc(model, 4, 10, 1, 0.1, 1.0)
+        for nwv in (0, 3, 5, 8, -2):
+            assert call(d, plain, nwv) < 0 and b"nwv" in lib.vissm_last_error(), (model, nwv)
+        d0 = _lib.ElboDesc(model, 0, 10, 1, 0.1, 1.0)
+        for nwv in (1, 2, 4):
+            assert call(d0, plain, nwv) == 0
+            if model != _lib.MODEL_SV:
+                assert call(d, listed, nwv) < 0 if nwv > 1 else call(d0, listed, nwv) == 0
+                assert nwv == 1 or b"obs_list" in lib.vissm_last_error()
+    d = _lib.ElboDesc(_lib.MODEL_AR, 4, 10, 1, 1.0, 1.0)
+    for nwv in (2, 4):
+        assert call(d, plain, nwv) < 0 and b"AR" in lib.vissm_last_error()
+    assert call(_lib.ElboDesc(_lib.MODEL_AR, 0, 10, 1, 1.0, 1.0), plain, 1) == 0
+
+
 def test_bf16x2_precisions_without_gpu():
     """VISSM_PREC_BF16X2 (split weights, bf16 activations) is a forward and backward precision with workspace on
     both sides; VISSM_PREC_BF16X2_BF16 belongs to the fused last AR flow only and the other entry points refuse it

@@ -186,6 +186,8 @@ SIGNATURES = {
                               _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "vissm_elbo_fwd_theta_grad": (_i32, [ctypes.POINTER(ElboDesc), ctypes.POINTER(ElboData)] + [_c_void_p] * 10),
     "vissm_elbo_fwd_grad": (_i32, [ctypes.POINTER(ElboDesc), ctypes.POINTER(ElboData)] + [_c_void_p] * 11),
+    "vissm_elbo_fwd_grad_nwv": (_i32, [ctypes.POINTER(ElboDesc), ctypes.POINTER(ElboData)] + [_c_void_p] * 10 +
+                                [_i32, _c_void_p]),
     "vissm_adamax_workspace_size": (_size_t, [_i64]),
     "vissm_adamax_step": (_i32, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _f32, _f32, _f32, _f32,
                                  _f32, _c_void_p, _c_void_p, _size_t, _c_void_p]),

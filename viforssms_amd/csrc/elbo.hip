@@ -1329,19 +1329,23 @@ static int onepass_waves(const VissmElboDesc* d) {
 
 extern "C" {
 
-int vissm_elbo_fwd_grad(const VissmElboDesc* d, const VissmElboData* data, const float* z, const float* theta,
-                        const float* g_sde, const float* g_obs, const float* g_extra, float* sde, float* obs,
-                        float* extra, float* dz, float* dtheta, void* stream) {
+int vissm_elbo_fwd_grad_nwv(const VissmElboDesc* d, const VissmElboData* data, const float* z, const float* theta,
+                            const float* g_sde, const float* g_obs, const float* g_extra, float* sde, float* obs,
+                            float* extra, float* dz, float* dtheta, int32_t nwv, void* stream) {
   int rc = check(d, data);
   if (rc) return rc;
   VISSM_CHECK_ARG(z && theta && sde && dz && dtheta, "elbo_fwd_grad: null pointer");
+  VISSM_CHECK_ARG(nwv == 1 || nwv == 2 || nwv == 4, "elbo_fwd_grad: nwv = %d (1, 2 or 4 waves per trajectory)", nwv);
+  VISSM_CHECK_ARG(nwv == 1 || d->model != VISSM_MODEL_AR, "elbo_fwd_grad: AR has one wave per trajectory (nwv = %d)",
+                  nwv);
+  const bool ol = data->obs_list != nullptr && (d->model == VISSM_MODEL_LV || d->model == VISSM_MODEL_FHN);
+  VISSM_CHECK_ARG(nwv == 1 || !ol, "elbo_fwd_grad: obs_list needs one wave per trajectory (nwv = %d)", nwv);
   if (d->B == 0) return VISSM_OK;
   VISSM_CHECK_ARG(!data->obs_list || data->obs_stride > 0, "elbo_fwd_grad: obs_list needs obs_stride > 0");
   Args a = make(d, data);
   hipStream_t st = as_stream(stream);
   dim3 grid((d->B + kSW - 1) / kSW), blk(256);
   const Vals vo{sde, obs, extra};
-  const bool ol = data->obs_list != nullptr && (d->model == VISSM_MODEL_LV || d->model == VISSM_MODEL_FHN);
   prof_begin(VISSM_PROF_ELBO_BWD, st);
   switch (d->model) {
     case VISSM_MODEL_AR:
@@ -1354,9 +1358,8 @@ int vissm_elbo_fwd_grad(const VissmElboDesc* d, const VissmElboData* data, const
                      z, theta, g_sde, g_obs, g_extra, dz, dtheta, vo)
 #define ONEPASS_NWV(MODEL_)                                                                                       \
   do {                                                                                                           \
-    const int nwv_ = onepass_waves(d);                                                                           \
-    if (nwv_ == 4) ONEPASS(MODEL_, false, 4);                                                                    \
-    else if (nwv_ == 2) ONEPASS(MODEL_, false, 2);                                                               \
+    if (nwv == 4) ONEPASS(MODEL_, false, 4);                                                                     \
+    else if (nwv == 2) ONEPASS(MODEL_, false, 2);                                                                \
     else ONEPASS(MODEL_, false, 1);                                                                              \
   } while (0)
     case VISSM_MODEL_LV:
@@ -1380,6 +1383,17 @@ int vissm_elbo_fwd_grad(const VissmElboDesc* d, const VissmElboData* data, const
   // algorithmic bytes: z read once, dz written, theta / dtheta, the upstream gradients and the three sums
   prof_end(VISSM_PROF_ELBO_BWD, st, 4.0 * d->B * (2.0 * zlen_of(d) + 2 * theta_len(d->model) + 6));
   return VISSM_OK;
+}
+
+// the library's own choice of waves per trajectory; an observation list (LV / FHN) and AR run one wave per trajectory
+int vissm_elbo_fwd_grad(const VissmElboDesc* d, const VissmElboData* data, const float* z, const float* theta,
+                        const float* g_sde, const float* g_obs, const float* g_extra, float* sde, float* obs,
+                        float* extra, float* dz, float* dtheta, void* stream) {
+  int nwv = 1;
+  if (d && data && d->model != VISSM_MODEL_AR &&
+      !(data->obs_list && (d->model == VISSM_MODEL_LV || d->model == VISSM_MODEL_FHN)))
+    nwv = onepass_waves(d);
+  return vissm_elbo_fwd_grad_nwv(d, data, z, theta, g_sde, g_obs, g_extra, sde, obs, extra, dz, dtheta, nwv, stream);
 }
 
 int vissm_elbo_fwd_theta_grad(const VissmElboDesc* d, const VissmElboData* data, const float* z, const float* theta,

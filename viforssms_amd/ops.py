@@ -718,20 +718,22 @@ def elbo_values_and_theta_grad(model: int, M: int, dt: float, obs_std: float, fe
         check(lib.vissm_elbo_fwd(ctypes.byref(d), ctypes.byref(data), ptr(z), ptr(theta), ptr(sde), ptr(obs),
                                  ptr(extra), st), "vissm_elbo_fwd")
         check(lib.vissm_elbo_bwd(ctypes.byref(d), ctypes.byref(data), ptr(z), ptr(theta), ptr(g_sde), ptr(g_obs),
-                                 ptr(extra), None, ptr(dth), st), "vissm_elbo_bwd")
+                                 None, None, ptr(dth), st), "vissm_elbo_bwd")
         return sde, obs, dth
     # one pass over z for AR(1) (vissm_elbo_fwd then vissm_elbo_bwd with dz = NULL for the other models)
     check(lib.vissm_elbo_fwd_theta_grad(ctypes.byref(d), ctypes.byref(data), ptr(z), ptr(theta), ptr(g_sde),
-                                        ptr(g_obs), ptr(extra), ptr(sde), ptr(obs), ptr(extra), ptr(dth), st),
+                                        ptr(g_obs), None, ptr(sde), ptr(obs), ptr(extra), ptr(dth), st),
           "vissm_elbo_fwd_theta_grad")
     return sde, obs, dth
 
 
 def elbo_values_grad(model: int, M: int, dt: float, obs_std: float, feeds: ElboFeeds, z, theta,
-                     g_sde: torch.Tensor, g_obs: Optional[torch.Tensor], g_extra: Optional[torch.Tensor]):
+                     g_sde: torch.Tensor, g_obs: Optional[torch.Tensor], g_extra: Optional[torch.Tensor],
+                     nwv: Optional[int] = None):
     """(sde, obs, extra) per sample, dz and dtheta of g_sde . sde + g_obs . obs + g_extra . extra in ONE pass over z
     (vissm_elbo_fwd_grad): the training step knows these upstream gradients before the forward.  No autograd: the
-    caller feeds dz / dtheta into a multi-root backward (Engine.forward_onepass)."""
+    caller feeds dz / dtheta into a multi-root backward (Engine.forward_onepass).  nwv (1, 2 or 4): the LV / SV / FHN
+    kernel's waves per trajectory through vissm_elbo_fwd_grad_nwv; None: the library's choice."""
     lib = _lib.load()
     _require_gpu(z, theta, g_sde, feeds.obs, feeds.obs_bin, feeds.mask, feeds.shift, feeds.dim_one, feeds.win,
                  feeds.plain_from, feeds.obs_list)
@@ -744,6 +746,11 @@ def elbo_values_grad(model: int, M: int, dt: float, obs_std: float, feeds: ElboF
     z = z.contiguous()
     dz = torch.empty_like(z)
     dth = torch.empty_like(theta)
+    if nwv is not None:
+        check(lib.vissm_elbo_fwd_grad_nwv(ctypes.byref(d), ctypes.byref(data), ptr(z), ptr(theta), ptr(g_sde),
+                                          ptr(g_obs), ptr(g_extra), ptr(sde), ptr(obs), ptr(extra), ptr(dz), ptr(dth),
+                                          int(nwv), _lib.stream_handle(z.device)), "vissm_elbo_fwd_grad_nwv")
+        return sde, obs, extra, dz, dth
     check(lib.vissm_elbo_fwd_grad(ctypes.byref(d), ctypes.byref(data), ptr(z), ptr(theta), ptr(g_sde), ptr(g_obs),
                                   ptr(g_extra), ptr(sde), ptr(obs), ptr(extra), ptr(dz), ptr(dth),
                                   _lib.stream_handle(z.device)), "vissm_elbo_fwd_grad")
