@@ -1,6 +1,6 @@
-"""Compare the kernels of two builds of the same translation units, from their device assembly.
+r"""Compare the kernels of two builds of the same translation units, from their device assembly.
 
-usage: python scripts/compare_kernel_asm.py [--summary] PARENT_DIR CHANGE_DIR
+usage: python scripts/compare_kernel_asm.py [--summary] [--pair P=C ...] [--mask-kernarg] PARENT_DIR CHANGE_DIR
 Each directory holds one <unit>.s per translation unit (the Makefile's compile line of the unit plus
 --cuda-device-only -S).  For every kernel of CHANGE_DIR/<unit>.s the script looks up the kernel of the same name in
 PARENT_DIR/<unit>.s and compares
@@ -10,7 +10,17 @@ PARENT_DIR/<unit>.s and compares
 It prints one line per kernel and a total, and exits with status 1 if a kernel is missing from the parent or differs.
 Kernels that only the parent has are counted (the change compiles fewer), not listed.
 With --summary, a kernel that differs is followed by what moved, parent -> change: the instruction counts, the
-opcodes whose counts differ and the .amdhsa_ lines that differ.  The verdict lines and the exit status are the same."""
+opcodes whose counts differ and the .amdhsa_ lines that differ.  The verdict lines and the exit status are the same.
+
+For a change that renames kernels or gives them other arguments (the mangled name holds both):
+  --pair PARENT_REGEX=CHANGE_REGEX  (repeatable) a kernel of the change that has no namesake and that CHANGE_REGEX
+      matches is compared with the one kernel of the parent that PARENT_REGEX matches with the same groups, e.g.
+      --pair '20pmmh_adaptive_kernelI((?:Li\d+E)+)EEv=11pmmh_kernelI((?:Li\d+E)+)Lb1EEEv' (mangled names: a kernel
+      that became the <.., true> instantiation of another template); its line is followed by the parent's name.
+  --mask-kernarg  a kernel that differs from its parent only in the offset operands of its scalar loads from the
+      kernarg segment pointer and in .amdhsa_kernarg_size (a longer or reordered argument list moves these and nothing
+      else) gets the verdict `same but kernarg` and counts as passing; the total names the two counts apart."""
+import argparse
 import collections
 import os
 import re
@@ -58,33 +68,71 @@ def summary(old, new):
     return out
 
 
+def partner(name, old, pairs):
+    """The parent's kernel for the change's kernel `name`: the one of that name, else, for the first --pair whose
+    CHANGE_REGEX matches `name`, the one parent kernel that its PARENT_REGEX matches with the same groups."""
+    if name in old:
+        return name
+    for parent_re, change_re in pairs:
+        m = change_re.search(name)
+        if m:
+            found = [k for k in old if (p := parent_re.search(k)) and p.groups() == m.groups()]
+            return found[0] if len(found) == 1 else None
+    return None
+
+
+def mask_kernarg(kernel):
+    """(instruction lines, .amdhsa_ lines) without what the length and order of the kernel's argument list decide: the
+    offset operand of the scalar loads from the kernarg segment pointer (the user SGPR pair that follows the private
+    segment buffer, the dispatch pointer and the queue pointer, as the .amdhsa_user_sgpr_ lines enable them) and the
+    .amdhsa_kernarg_size line."""
+    body, res = kernel
+    on = {k: v for k, v in (l.split(None, 1) for l in res)}
+    first = 4 * int(on.get(".amdhsa_user_sgpr_private_segment_buffer", 0)) + \
+        2 * int(on.get(".amdhsa_user_sgpr_dispatch_ptr", 0)) + 2 * int(on.get(".amdhsa_user_sgpr_queue_ptr", 0))
+    load = re.compile(rf"^(s_load_\w+\s+\S+,\s*s\[{first}:{first + 1}\]),\s*\S+$")
+    return ([load.sub(r"\1, <kernarg>", l) for l in body],
+            [l for l in res if not l.startswith(".amdhsa_kernarg_size ")])
+
+
 def main():
-    args = [a for a in sys.argv[1:] if a != "--summary"]
-    if len(args) != 2:
-        raise SystemExit(__doc__)
-    parent_dir, change_dir = args
-    want_summary = "--summary" in sys.argv[1:]
-    n = same = dropped = 0
-    for unit in sorted(f for f in os.listdir(change_dir) if f.endswith(".s")):
-        new = kernels(os.path.join(change_dir, unit))
-        old = kernels(os.path.join(parent_dir, unit))
-        dropped += len(set(old) - set(new))
+    ap = argparse.ArgumentParser(usage=__doc__)
+    ap.add_argument("--summary", action="store_true")
+    ap.add_argument("--pair", action="append", default=[], metavar="PARENT_REGEX=CHANGE_REGEX")
+    ap.add_argument("--mask-kernarg", action="store_true")
+    ap.add_argument("parent_dir")
+    ap.add_argument("change_dir")
+    args = ap.parse_args()
+    pairs = [tuple(re.compile(r) for r in p.split("=", 1)) for p in args.pair]
+    n = same = kernarg = dropped = 0
+    for unit in sorted(f for f in os.listdir(args.change_dir) if f.endswith(".s")):
+        new = kernels(os.path.join(args.change_dir, unit))
+        old = kernels(os.path.join(args.parent_dir, unit))
+        mate = {name: partner(name, old, pairs) for name in new}
+        dropped += len(set(old) - set(mate.values()))
         for name in sorted(new):
             n += 1
-            if name not in old:
+            was = old.get(mate[name])
+            if was is None:
                 verdict = "NOT IN PARENT"
             else:
-                code = new[name][0] == old[name][0]
-                regs = new[name][1] == old[name][1]
+                code, regs = new[name][0] == was[0], new[name][1] == was[1]
                 verdict = "same" if code and regs else " ".join(
                     (["CODE DIFFERS"] if not code else []) + (["RESOURCES DIFFER"] if not regs else []))
                 same += code and regs
+                if args.mask_kernarg and verdict != "same" and mask_kernarg(new[name]) == mask_kernarg(was):
+                    verdict = "same but kernarg"
+                    kernarg += 1
             print(f"{unit[:-2]:9s} {len(new[name][0]):6d} instr  {verdict:13s} {name}")
-            if want_summary and name in old and verdict != "same":
-                print("\n".join(summary(old[name], new[name])))
-    print(f"total: {n} kernels in the change, {same} the same as in the parent, {n - same} differ or are new; "
-          f"{dropped} kernels of the parent no longer compiled")
-    sys.exit(0 if n and same == n else 1)
+            if was is not None and mate[name] != name:
+                print(f"    parent: {mate[name]}")
+            if args.summary and was is not None and verdict != "same":
+                print("\n".join(summary(was, new[name])))
+    ok = same + kernarg
+    print(f"total: {n} kernels in the change, {same} the same as in the parent, " +
+          (f"{kernarg} the same but for kernarg offsets and size, " if args.mask_kernarg else "") +
+          f"{n - ok} differ or are new; {dropped} kernels of the parent no longer compiled")
+    sys.exit(0 if n and ok == n else 1)
 
 
 if __name__ == "__main__":

@@ -289,9 +289,9 @@ int hc_mh_accept(double logu, double ll_prop, double ll_cur, double lp_prop, dou
   return vissm::mh::accept(logu, ll_prop, ll_cur, lp_prop, lp_cur) ? 1 : 0;
 }
 
-// The adaptive chain's update (mh_math.hpp: the code pmmh_adaptive_kernel's thread 0 runs).  hc_mh_alpha: the
-// acceptance probability from the state before the decision; hc_mh_eta: the step size of the absolute iteration i;
-// hc_mh_adapt: L [P][P] -> L' in place from the normals xi [P], returns 1 when L changed, 0 when it was kept.
+// The adaptive chain's update (mh_math.hpp: the code thread 0 of pmmh_kernel<.., ADAPT = true> runs).  hc_mh_alpha:
+// the acceptance probability from the state before the decision; hc_mh_eta: the step size of the absolute iteration
+// i; hc_mh_adapt: L [P][P] -> L' in place from the normals xi [P], returns 1 when L changed, 0 when it was kept.
 double hc_mh_alpha(double ll_prop, double ll_cur, double lp_prop, double lp_cur) {
   return vissm::mh::accept_prob(ll_prop, ll_cur, lp_prop, lp_cur);
 }

@@ -1276,134 +1276,6 @@ class PmmhResult:
     logu: Optional[torch.Tensor]         # [C, n_iter] float64 the logs of the decisions' uniforms, or None
 
 
-def pmmh(model_id: int, theta_cur: torch.Tensor, ll_cur: torch.Tensor, prop_chol: torch.Tensor, prior: torch.Tensor,
-         x_start: torch.Tensor, obs: torch.Tensor, obs_bin: torch.Tensor, dt: float, obs_std: float, N: int,
-         n_iter: int, seed: int, row0: int, it0: int = 0, trace: bool = False) -> PmmhResult:
-    """n_iter iterations of C particle marginal Metropolis-Hastings chains, one per row of theta_cur [C, P] (raw, as
-    the ELBO takes it); vissm_pmmh: one block per chain, the whole chain in one launch.  An iteration proposes
-    theta' = theta + L xi with prop_chol = L [P, P] (lower), estimates log p(y | theta') with the fully adapted filter
-    of N particles over obs / obs_bin [S, T] from x_start [S], and accepts iff log u < (ll' - ll) + (lp' - lp), lp the
-    independent Gaussian log-prior of prior [P, 2] = (mean, sd).  ll_cur [C] float64 is the estimate that goes with
-    theta_cur: particle_filter(proposal="adapted", cloud=False).loglik.  Iteration i of chain c uses the Philox rows
-    row0 + (i C + c) N .. + N - 1: its filter is particle_filter's for K = C at row0 + i C N, its proposal and uniform
-    sit on counter word 1 = 2 of the first of them.  A call with it0' = it0 + n_iter, theta_cur = theta_end and ll_cur =
-    ll_end continues bitwise.  trace: also the proposals, their estimates and log u.  AR, LV and FHN."""
-    # the refusals of the C entry, by host arithmetic before any GPU call
-    if model_id == _lib.MODEL_SV:
-        raise ValueError("pmmh: no observation model for SV (its first coordinate is the observed series)")
-    if model_id not in _lib.MODEL_S:
-        raise ValueError(f"pmmh: unknown model {model_id}")
-    S, P = _lib.MODEL_S[model_id], _lib.MODEL_P[model_id]
-    N, n_iter, it0 = int(N), int(n_iter), int(it0)
-    if N not in _lib.PF_PARTICLES:
-        raise ValueError(f"pmmh: N={N} particles, one of {_lib.PF_PARTICLES} expected")
-    if not 0.0 < float(obs_std) < float("inf"):
-        raise ValueError(f"pmmh: a positive, finite obs_std expected, got {obs_std}")
-    if theta_cur.dim() != 2 or theta_cur.shape[1] != P or theta_cur.shape[0] < 1:
-        raise ValueError(f"pmmh: theta_cur [C >= 1, {P}] expected, got {tuple(theta_cur.shape)}")
-    C = theta_cur.shape[0]
-    if n_iter < 0 or it0 < 0 or it0 + n_iter >= 2 ** 31:
-        raise ValueError(f"pmmh: bad iterations it0={it0} n_iter={n_iter}")
-    if obs.dim() != 2 or obs.shape[0] != S or obs_bin.shape != obs.shape:
-        raise ValueError(f"pmmh: obs and obs_bin [{S}, T] expected, got {tuple(obs.shape)} and "
-                         f"{tuple(obs_bin.shape)}")
-    T_total = obs.shape[1]
-    if T_total * S >= 2 ** 31:
-        raise ValueError(f"pmmh: T S = {T_total} * {S} reaches 2^31")
-    if not 0 <= int(row0) < 2 ** 64:
-        raise ValueError(f"pmmh: row0={row0} outside [0, 2^64)")
-    _require_gpu(theta_cur, prop_chol, prior, x_start, obs, obs_bin)
-    for name, t, shape in (("theta_cur", theta_cur, (C, P)), ("prop_chol", prop_chol, (P, P)),
-                           ("prior", prior, (P, 2)), ("x_start", x_start, (S,)), ("obs", obs, (S, T_total)),
-                           ("obs_bin", obs_bin, (S, T_total))):
-        if t.dtype != torch.float32 or tuple(t.shape) != shape:
-            raise ValueError(f"pmmh: fp32 {name} {list(shape)} expected, got {t.dtype} {tuple(t.shape)}")
-    dev = theta_cur.device
-    if not ll_cur.is_cuda or ll_cur.dtype != torch.float64 or tuple(ll_cur.shape) != (C,) or \
-            not ll_cur.is_contiguous():
-        raise ValueError(f"pmmh: ll_cur: a contiguous float64 GPU tensor [{C}] expected")
-    if any(t.device != dev for t in (ll_cur, prop_chol, prior, x_start, obs, obs_bin)):
-        raise ValueError("pmmh: all tensors on one device expected")
-    key, row = ctypes.c_uint64(seed & (2 ** 64 - 1)), ctypes.c_uint64(int(row0))
-    theta_chain = torch.empty(C, n_iter, P, dtype=torch.float32, device=dev)
-    ll_chain = torch.empty(C, n_iter, dtype=torch.float64, device=dev)
-    accept = torch.empty(C, n_iter, dtype=torch.int32, device=dev)
-    theta_end = torch.empty(C, P, dtype=torch.float32, device=dev)
-    ll_end = torch.empty(C, dtype=torch.float64, device=dev)
-    tp = torch.empty(C, n_iter, P, dtype=torch.float32, device=dev) if trace else None
-    lpr = torch.empty(C, n_iter, dtype=torch.float64, device=dev) if trace else None
-    lu = torch.empty(C, n_iter, dtype=torch.float64, device=dev) if trace else None
-    d = _lib.PmmhDesc(model_id, C, N, n_iter, it0, T_total, float(dt), float(obs_std))
-    check(_lib.load().vissm_pmmh(ctypes.byref(d), key, row, ptr(theta_cur), ptr(ll_cur), ptr(prop_chol), ptr(prior),
-                                 ptr(x_start), ptr(obs), ptr(obs_bin), ptr(theta_chain), ptr(ll_chain), ptr(accept),
-                                 ptr(theta_end), ptr(ll_end), ptr(tp), ptr(lpr), ptr(lu), _lib.stream_handle(dev)),
-          "vissm_pmmh")
-    return PmmhResult(theta_chain, ll_chain, accept, theta_end, ll_end, tp, lpr, lu)
-
-
-def sv_pmmh(theta_cur: torch.Tensor, ll_cur: torch.Tensor, prop_chol: torch.Tensor, prior: torch.Tensor,
-            h_start: torch.Tensor, obs: torch.Tensor, dt: float, N: int, n_iter: int, seed: int, row0: int,
-            it0: int = 0, trace: bool = False) -> PmmhResult:
-    """pmmh for the stochastic-volatility model, which pmmh refuses: n_iter iterations of C chains, one per row of
-    theta_cur [C, 4] (raw); vissm_sv_pmmh: one block per chain, the whole chain in one launch.  An iteration proposes
-    theta' = theta + L xi with prop_chol = L [4, 4] (lower), estimates log p(y | theta') with sv_filter's filter of N
-    particles (exactly fully adapted) over the series obs = y[0 .. T] (T + 1 values), every particle started at
-    h_start [1], and accepts iff log u < (ll' - ll) + (lp' - lp), lp the independent Gaussian log-prior of
-    prior [4, 2] = (mean, sd).  ll_cur [C] float64 is the estimate that goes with theta_cur:
-    sv_filter(cloud=False).loglik.  Iteration i of chain c uses the Philox rows row0 + (i C + c) N .. + N - 1: its
-    filter is sv_filter's for K = C at row0 + i C N, its proposal and uniform sit on counter word 1 = 2 of the first of
-    them.  A call with it0' = it0 + n_iter, theta_cur = theta_end and ll_cur = ll_end continues bitwise.  trace: also
-    the proposals, their estimates and log u."""
-    # the refusals of the C entry, by host arithmetic before any GPU call
-    P = _lib.MODEL_P[_lib.MODEL_SV]
-    N, n_iter, it0 = int(N), int(n_iter), int(it0)
-    if N not in _lib.PF_PARTICLES:
-        raise ValueError(f"sv_pmmh: N={N} particles, one of {_lib.PF_PARTICLES} expected")
-    if not 0.0 < float(dt) < float("inf"):
-        raise ValueError(f"sv_pmmh: dt must be positive and finite, got {dt}")
-    if theta_cur.dim() != 2 or theta_cur.shape[1] != P or theta_cur.shape[0] < 1:
-        raise ValueError(f"sv_pmmh: theta_cur [C >= 1, {P}] expected, got {tuple(theta_cur.shape)}")
-    C = theta_cur.shape[0]
-    if n_iter < 0 or it0 < 0 or it0 + n_iter >= 2 ** 31:
-        raise ValueError(f"sv_pmmh: bad iterations it0={it0} n_iter={n_iter}")
-    if obs.dim() != 1 or obs.shape[0] < 1 or obs.dtype != torch.float32:
-        raise ValueError(f"sv_pmmh: obs: an fp32 vector y[0 .. T] expected, got {obs.dtype} {tuple(obs.shape)}")
-    T_total = obs.shape[0] - 1
-    if T_total >= 2 ** 31 - 1:
-        raise ValueError(f"sv_pmmh: T = {T_total} reaches 2^31 - 1")
-    if not 0 <= int(row0) < 2 ** 64:
-        raise ValueError(f"sv_pmmh: row0={row0} outside [0, 2^64)")
-    _require_gpu(theta_cur, prop_chol, prior, h_start, obs)
-    for name, t, shape in (("theta_cur", theta_cur, (C, P)), ("prop_chol", prop_chol, (P, P)),
-                           ("prior", prior, (P, 2)), ("h_start", h_start, (1,))):
-        if t.dtype != torch.float32 or tuple(t.shape) != shape:
-            raise ValueError(f"sv_pmmh: fp32 {name} {list(shape)} expected, got {t.dtype} {tuple(t.shape)}")
-    dev = theta_cur.device
-    if not ll_cur.is_cuda or ll_cur.dtype != torch.float64 or tuple(ll_cur.shape) != (C,) or \
-            not ll_cur.is_contiguous():
-        raise ValueError(f"sv_pmmh: ll_cur: a contiguous float64 GPU tensor [{C}] expected")
-    if any(t.device != dev for t in (ll_cur, prop_chol, prior, h_start, obs)):
-        raise ValueError("sv_pmmh: all tensors on one device expected")
-    key, row = ctypes.c_uint64(seed & (2 ** 64 - 1)), ctypes.c_uint64(int(row0))
-    theta_chain = torch.empty(C, n_iter, P, dtype=torch.float32, device=dev)
-    ll_chain = torch.empty(C, n_iter, dtype=torch.float64, device=dev)
-    accept = torch.empty(C, n_iter, dtype=torch.int32, device=dev)
-    theta_end = torch.empty(C, P, dtype=torch.float32, device=dev)
-    ll_end = torch.empty(C, dtype=torch.float64, device=dev)
-    tp = torch.empty(C, n_iter, P, dtype=torch.float32, device=dev) if trace else None
-    lpr = torch.empty(C, n_iter, dtype=torch.float64, device=dev) if trace else None
-    lu = torch.empty(C, n_iter, dtype=torch.float64, device=dev) if trace else None
-    d = _lib.PmmhDesc(_lib.MODEL_SV, C, N, n_iter, it0, T_total, float(dt), 0.0)
-    check(_lib.load().vissm_sv_pmmh(ctypes.byref(d), key, row, ptr(theta_cur), ptr(ll_cur), ptr(prop_chol), ptr(prior),
-                                    ptr(h_start), ptr(obs), ptr(theta_chain), ptr(ll_chain), ptr(accept),
-                                    ptr(theta_end), ptr(ll_end), ptr(tp), ptr(lpr), ptr(lu), _lib.stream_handle(dev)),
-          "vissm_sv_pmmh")
-    return PmmhResult(theta_chain, ll_chain, accept, theta_end, ll_end, tp, lpr, lu)
-
-
-# ---------------------------------------------------------------------------------------
-# adaptive particle marginal Metropolis-Hastings (each chain learns its own proposal factor)
-# ---------------------------------------------------------------------------------------
 @dataclass
 class PmmhAdaptiveResult(PmmhResult):
     chol_end: torch.Tensor = None               # [C, P, P]: chol_in of the call that continues at it0 + n_iter
@@ -1425,21 +1297,124 @@ def _adaptive_args(what: str, adapt_end, target_accept, gamma) -> tuple:
     return adapt_end, target_accept, gamma
 
 
-def _adaptive_outputs(C: int, n_iter: int, P: int, trace: bool, dev):
-    """The output tensors of an adaptive launch, in the C entry's order."""
+def _pmmh_chain(what: str, sv: bool, model_id: int, theta_cur, ll_cur, chol, prior, x_start, obs, obs_bin, dt, obs_std,
+                N, n_iter, seed, row0, it0, trace: bool, adapt: Optional[tuple] = None):
+    """pmmh, sv_pmmh, pmmh_adaptive and sv_pmmh_adaptive: `what` is the function's name (vissm_<what> its C entry), sv
+    says whether the series is the stochastic-volatility model's y[0 .. T] (x_start is then h_start [1], obs_bin None
+    and obs_std unused), adapt is None (chol is prop_chol [P, P]) or (adapt_end, target_accept, gamma) (chol is
+    chol_in [C, P, P]).  The refusals of the C entry, by host arithmetic before any GPU call; then the outputs and the
+    launch."""
+    if not sv:
+        if model_id == _lib.MODEL_SV:
+            raise ValueError(f"{what}: no observation model for SV (its first coordinate is the observed series)")
+        if model_id not in _lib.MODEL_S:
+            raise ValueError(f"{what}: unknown model {model_id}")
+    S, P = _lib.MODEL_S[model_id], _lib.MODEL_P[model_id]
+    N, n_iter, it0 = int(N), int(n_iter), int(it0)
+    if N not in _lib.PF_PARTICLES:
+        raise ValueError(f"{what}: N={N} particles, one of {_lib.PF_PARTICLES} expected")
+    if sv:
+        if not 0.0 < float(dt) < float("inf"):
+            raise ValueError(f"{what}: dt must be positive and finite, got {dt}")
+    elif not 0.0 < float(obs_std) < float("inf"):
+        raise ValueError(f"{what}: a positive, finite obs_std expected, got {obs_std}")
+    if theta_cur.dim() != 2 or theta_cur.shape[1] != P or theta_cur.shape[0] < 1:
+        raise ValueError(f"{what}: theta_cur [C >= 1, {P}] expected, got {tuple(theta_cur.shape)}")
+    C = theta_cur.shape[0]
+    if n_iter < 0 or it0 < 0 or it0 + n_iter >= 2 ** 31:
+        raise ValueError(f"{what}: bad iterations it0={it0} n_iter={n_iter}")
+    if adapt is not None:
+        adapt = _adaptive_args(what, *adapt)
+    if sv:
+        if obs.dim() != 1 or obs.shape[0] < 1 or obs.dtype != torch.float32:
+            raise ValueError(f"{what}: obs: an fp32 vector y[0 .. T] expected, got {obs.dtype} {tuple(obs.shape)}")
+        T_total = obs.shape[0] - 1
+        if T_total >= 2 ** 31 - 1:
+            raise ValueError(f"{what}: T = {T_total} reaches 2^31 - 1")
+        series, shaped = [obs], [("h_start", x_start, (1,))]
+    else:
+        if obs.dim() != 2 or obs.shape[0] != S or obs_bin.shape != obs.shape:
+            raise ValueError(f"{what}: obs and obs_bin [{S}, T] expected, got {tuple(obs.shape)} and "
+                             f"{tuple(obs_bin.shape)}")
+        T_total = obs.shape[1]
+        if T_total * S >= 2 ** 31:
+            raise ValueError(f"{what}: T S = {T_total} * {S} reaches 2^31")
+        series = [obs, obs_bin]
+        shaped = [("x_start", x_start, (S,)), ("obs", obs, (S, T_total)), ("obs_bin", obs_bin, (S, T_total))]
+    if not 0 <= int(row0) < 2 ** 64:
+        raise ValueError(f"{what}: row0={row0} outside [0, 2^64)")
+    if adapt is None:  # (prop_chol takes its turn below)
+        shaped = [("prop_chol", chol, (P, P)), ("prior", prior, (P, 2))] + shaped
+    else:
+        if chol.dtype != torch.float32 or tuple(chol.shape) != (C, P, P):
+            raise ValueError(f"{what}: fp32 chol_in {[C, P, P]} expected, got {chol.dtype} {tuple(chol.shape)}")
+        shaped = [("prior", prior, (P, 2))] + shaped
+    _require_gpu(theta_cur, chol, prior, x_start, *series)
+    for name, x, shape in [("theta_cur", theta_cur, (C, P))] + shaped:
+        if x.dtype != torch.float32 or tuple(x.shape) != shape:
+            raise ValueError(f"{what}: fp32 {name} {list(shape)} expected, got {x.dtype} {tuple(x.shape)}")
+    dev = theta_cur.device
+    if not ll_cur.is_cuda or ll_cur.dtype != torch.float64 or tuple(ll_cur.shape) != (C,) or \
+            not ll_cur.is_contiguous():
+        raise ValueError(f"{what}: ll_cur: a contiguous float64 GPU tensor [{C}] expected")
+    if any(t.device != dev for t in (ll_cur, chol, prior, x_start, *series)):
+        raise ValueError(f"{what}: all tensors on one device expected")
+    key, row = ctypes.c_uint64(seed & (2 ** 64 - 1)), ctypes.c_uint64(int(row0))
     f32, f64 = torch.float32, torch.float64
     e = lambda *shape, dtype=f32: torch.empty(*shape, dtype=dtype, device=dev)
     t = lambda *shape, dtype=f32: e(*shape, dtype=dtype) if trace else None
-    return [e(C, n_iter, P), e(C, n_iter, dtype=f64), e(C, n_iter, dtype=torch.int32), e(C, P), e(C, dtype=f64),
-            e(C, P, P), t(C, n_iter, P), t(C, n_iter, dtype=f64), t(C, n_iter, dtype=f64), t(C, n_iter, 8),
-            t(C, n_iter, dtype=f64), t(C, n_iter, dtype=f64), t(C, n_iter, P, P)]
+    chain = [e(C, n_iter, P), e(C, n_iter, dtype=f64), e(C, n_iter, dtype=torch.int32), e(C, P), e(C, dtype=f64)]
+    traces = [t(C, n_iter, P), t(C, n_iter, dtype=f64), t(C, n_iter, dtype=f64)]
+    if adapt is None:
+        scalars, out, result = (), chain + traces, PmmhResult(*chain, *traces)
+    else:
+        chol_end = e(C, P, P)
+        more = [t(C, n_iter, 8), t(C, n_iter, dtype=f64), t(C, n_iter, dtype=f64), t(C, n_iter, P, P)]
+        scalars, out = adapt, chain + [chol_end] + traces + more
+        result = PmmhAdaptiveResult(*chain, *traces, chol_end, *more)
+    d = _lib.PmmhDesc(model_id, C, N, n_iter, it0, T_total, float(dt), float(obs_std))
+    entry = "vissm_" + what
+    check(getattr(_lib.load(), entry)(ctypes.byref(d), key, row, *map(ptr, (theta_cur, ll_cur, chol, prior, x_start)),
+                                      *map(ptr, series), *scalars, *map(ptr, out), _lib.stream_handle(dev)), entry)
+    return result
 
 
-def _adaptive_result(out) -> PmmhAdaptiveResult:
-    (theta_chain, ll_chain, accept, theta_end, ll_end, chol_end, tp, lpr, lu, xi, al, eta, ct) = out
-    return PmmhAdaptiveResult(theta_chain, ll_chain, accept, theta_end, ll_end, tp, lpr, lu, chol_end, xi, al, eta, ct)
+def pmmh(model_id: int, theta_cur: torch.Tensor, ll_cur: torch.Tensor, prop_chol: torch.Tensor, prior: torch.Tensor,
+         x_start: torch.Tensor, obs: torch.Tensor, obs_bin: torch.Tensor, dt: float, obs_std: float, N: int,
+         n_iter: int, seed: int, row0: int, it0: int = 0, trace: bool = False) -> PmmhResult:
+    """n_iter iterations of C particle marginal Metropolis-Hastings chains, one per row of theta_cur [C, P] (raw, as
+    the ELBO takes it); vissm_pmmh: one block per chain, the whole chain in one launch.  An iteration proposes
+    theta' = theta + L xi with prop_chol = L [P, P] (lower), estimates log p(y | theta') with the fully adapted filter
+    of N particles over obs / obs_bin [S, T] from x_start [S], and accepts iff log u < (ll' - ll) + (lp' - lp), lp the
+    independent Gaussian log-prior of prior [P, 2] = (mean, sd).  ll_cur [C] float64 is the estimate that goes with
+    theta_cur: particle_filter(proposal="adapted", cloud=False).loglik.  Iteration i of chain c uses the Philox rows
+    row0 + (i C + c) N .. + N - 1: its filter is particle_filter's for K = C at row0 + i C N, its proposal and uniform
+    sit on counter word 1 = 2 of the first of them.  A call with it0' = it0 + n_iter, theta_cur = theta_end and ll_cur =
+    ll_end continues bitwise.  trace: also the proposals, their estimates and log u.  AR, LV and FHN."""
+    return _pmmh_chain("pmmh", False, model_id, theta_cur, ll_cur, prop_chol, prior, x_start, obs, obs_bin, dt, obs_std,
+                       N, n_iter, seed, row0, it0, trace)
 
 
+def sv_pmmh(theta_cur: torch.Tensor, ll_cur: torch.Tensor, prop_chol: torch.Tensor, prior: torch.Tensor,
+            h_start: torch.Tensor, obs: torch.Tensor, dt: float, N: int, n_iter: int, seed: int, row0: int,
+            it0: int = 0, trace: bool = False) -> PmmhResult:
+    """pmmh for the stochastic-volatility model, which pmmh refuses: n_iter iterations of C chains, one per row of
+    theta_cur [C, 4] (raw); vissm_sv_pmmh: one block per chain, the whole chain in one launch.  An iteration proposes
+    theta' = theta + L xi with prop_chol = L [4, 4] (lower), estimates log p(y | theta') with sv_filter's filter of N
+    particles (exactly fully adapted) over the series obs = y[0 .. T] (T + 1 values), every particle started at
+    h_start [1], and accepts iff log u < (ll' - ll) + (lp' - lp), lp the independent Gaussian log-prior of
+    prior [4, 2] = (mean, sd).  ll_cur [C] float64 is the estimate that goes with theta_cur:
+    sv_filter(cloud=False).loglik.  Iteration i of chain c uses the Philox rows row0 + (i C + c) N .. + N - 1: its
+    filter is sv_filter's for K = C at row0 + i C N, its proposal and uniform sit on counter word 1 = 2 of the first of
+    them.  A call with it0' = it0 + n_iter, theta_cur = theta_end and ll_cur = ll_end continues bitwise.  trace: also
+    the proposals, their estimates and log u."""
+    return _pmmh_chain("sv_pmmh", True, _lib.MODEL_SV, theta_cur, ll_cur, prop_chol, prior, h_start, obs, None, dt, 0.0,
+                       N, n_iter, seed, row0, it0, trace)
+
+
+# ---------------------------------------------------------------------------------------
+# adaptive particle marginal Metropolis-Hastings (each chain learns its own proposal factor)
+# ---------------------------------------------------------------------------------------
 def pmmh_adaptive(model_id: int, theta_cur: torch.Tensor, ll_cur: torch.Tensor, chol_in: torch.Tensor,
                   prior: torch.Tensor, x_start: torch.Tensor, obs: torch.Tensor, obs_bin: torch.Tensor, dt: float,
                   obs_std: float, N: int, n_iter: int, seed: int, row0: int, adapt_end: int,
@@ -1454,53 +1429,8 @@ def pmmh_adaptive(model_id: int, theta_cur: torch.Tensor, ll_cur: torch.Tensor, 
     it0 + n_iter, theta_cur = theta_end, ll_cur = ll_end, chol_in = chol_end and the same adapt_end, target_accept and
     gamma continues bitwise.  trace: also pmmh's traces, the normals, alpha, eta and the factor after each
     iteration.  AR, LV and FHN."""
-    # the refusals of the C entry, by host arithmetic before any GPU call
-    what = "pmmh_adaptive"
-    if model_id == _lib.MODEL_SV:
-        raise ValueError(f"{what}: no observation model for SV (its first coordinate is the observed series)")
-    if model_id not in _lib.MODEL_S:
-        raise ValueError(f"{what}: unknown model {model_id}")
-    S, P = _lib.MODEL_S[model_id], _lib.MODEL_P[model_id]
-    N, n_iter, it0 = int(N), int(n_iter), int(it0)
-    if N not in _lib.PF_PARTICLES:
-        raise ValueError(f"{what}: N={N} particles, one of {_lib.PF_PARTICLES} expected")
-    if not 0.0 < float(obs_std) < float("inf"):
-        raise ValueError(f"{what}: a positive, finite obs_std expected, got {obs_std}")
-    if theta_cur.dim() != 2 or theta_cur.shape[1] != P or theta_cur.shape[0] < 1:
-        raise ValueError(f"{what}: theta_cur [C >= 1, {P}] expected, got {tuple(theta_cur.shape)}")
-    C = theta_cur.shape[0]
-    if n_iter < 0 or it0 < 0 or it0 + n_iter >= 2 ** 31:
-        raise ValueError(f"{what}: bad iterations it0={it0} n_iter={n_iter}")
-    adapt_end, target_accept, gamma = _adaptive_args(what, adapt_end, target_accept, gamma)
-    if obs.dim() != 2 or obs.shape[0] != S or obs_bin.shape != obs.shape:
-        raise ValueError(f"{what}: obs and obs_bin [{S}, T] expected, got {tuple(obs.shape)} and "
-                         f"{tuple(obs_bin.shape)}")
-    T_total = obs.shape[1]
-    if T_total * S >= 2 ** 31:
-        raise ValueError(f"{what}: T S = {T_total} * {S} reaches 2^31")
-    if not 0 <= int(row0) < 2 ** 64:
-        raise ValueError(f"{what}: row0={row0} outside [0, 2^64)")
-    if chol_in.dtype != torch.float32 or tuple(chol_in.shape) != (C, P, P):
-        raise ValueError(f"{what}: fp32 chol_in {[C, P, P]} expected, got {chol_in.dtype} {tuple(chol_in.shape)}")
-    _require_gpu(theta_cur, chol_in, prior, x_start, obs, obs_bin)
-    for name, t, shape in (("theta_cur", theta_cur, (C, P)), ("prior", prior, (P, 2)), ("x_start", x_start, (S,)),
-                           ("obs", obs, (S, T_total)), ("obs_bin", obs_bin, (S, T_total))):
-        if t.dtype != torch.float32 or tuple(t.shape) != shape:
-            raise ValueError(f"{what}: fp32 {name} {list(shape)} expected, got {t.dtype} {tuple(t.shape)}")
-    dev = theta_cur.device
-    if not ll_cur.is_cuda or ll_cur.dtype != torch.float64 or tuple(ll_cur.shape) != (C,) or \
-            not ll_cur.is_contiguous():
-        raise ValueError(f"{what}: ll_cur: a contiguous float64 GPU tensor [{C}] expected")
-    if any(t.device != dev for t in (ll_cur, chol_in, prior, x_start, obs, obs_bin)):
-        raise ValueError(f"{what}: all tensors on one device expected")
-    key, row = ctypes.c_uint64(seed & (2 ** 64 - 1)), ctypes.c_uint64(int(row0))
-    out = _adaptive_outputs(C, n_iter, P, trace, dev)
-    d = _lib.PmmhDesc(model_id, C, N, n_iter, it0, T_total, float(dt), float(obs_std))
-    check(_lib.load().vissm_pmmh_adaptive(ctypes.byref(d), key, row, ptr(theta_cur), ptr(ll_cur), ptr(chol_in),
-                                          ptr(prior), ptr(x_start), ptr(obs), ptr(obs_bin), adapt_end, target_accept,
-                                          gamma, *[ptr(t) for t in out], _lib.stream_handle(dev)),
-          "vissm_pmmh_adaptive")
-    return _adaptive_result(out)
+    return _pmmh_chain("pmmh_adaptive", False, model_id, theta_cur, ll_cur, chol_in, prior, x_start, obs, obs_bin, dt,
+                       obs_std, N, n_iter, seed, row0, it0, trace, (adapt_end, target_accept, gamma))
 
 
 def sv_pmmh_adaptive(theta_cur: torch.Tensor, ll_cur: torch.Tensor, chol_in: torch.Tensor, prior: torch.Tensor,
@@ -1511,44 +1441,5 @@ def sv_pmmh_adaptive(theta_cur: torch.Tensor, ll_cur: torch.Tensor, chol_in: tor
     adapted while the absolute iteration is below adapt_end and frozen after (vissm_sv_pmmh_adaptive).  Every other
     argument and every PmmhResult field is sv_pmmh's; the adaptation, chol_end, the chaining and the traces are
     pmmh_adaptive's."""
-    # the refusals of the C entry, by host arithmetic before any GPU call
-    what = "sv_pmmh_adaptive"
-    P = _lib.MODEL_P[_lib.MODEL_SV]
-    N, n_iter, it0 = int(N), int(n_iter), int(it0)
-    if N not in _lib.PF_PARTICLES:
-        raise ValueError(f"{what}: N={N} particles, one of {_lib.PF_PARTICLES} expected")
-    if not 0.0 < float(dt) < float("inf"):
-        raise ValueError(f"{what}: dt must be positive and finite, got {dt}")
-    if theta_cur.dim() != 2 or theta_cur.shape[1] != P or theta_cur.shape[0] < 1:
-        raise ValueError(f"{what}: theta_cur [C >= 1, {P}] expected, got {tuple(theta_cur.shape)}")
-    C = theta_cur.shape[0]
-    if n_iter < 0 or it0 < 0 or it0 + n_iter >= 2 ** 31:
-        raise ValueError(f"{what}: bad iterations it0={it0} n_iter={n_iter}")
-    adapt_end, target_accept, gamma = _adaptive_args(what, adapt_end, target_accept, gamma)
-    if obs.dim() != 1 or obs.shape[0] < 1 or obs.dtype != torch.float32:
-        raise ValueError(f"{what}: obs: an fp32 vector y[0 .. T] expected, got {obs.dtype} {tuple(obs.shape)}")
-    T_total = obs.shape[0] - 1
-    if T_total >= 2 ** 31 - 1:
-        raise ValueError(f"{what}: T = {T_total} reaches 2^31 - 1")
-    if not 0 <= int(row0) < 2 ** 64:
-        raise ValueError(f"{what}: row0={row0} outside [0, 2^64)")
-    if chol_in.dtype != torch.float32 or tuple(chol_in.shape) != (C, P, P):
-        raise ValueError(f"{what}: fp32 chol_in {[C, P, P]} expected, got {chol_in.dtype} {tuple(chol_in.shape)}")
-    _require_gpu(theta_cur, chol_in, prior, h_start, obs)
-    for name, t, shape in (("theta_cur", theta_cur, (C, P)), ("prior", prior, (P, 2)), ("h_start", h_start, (1,))):
-        if t.dtype != torch.float32 or tuple(t.shape) != shape:
-            raise ValueError(f"{what}: fp32 {name} {list(shape)} expected, got {t.dtype} {tuple(t.shape)}")
-    dev = theta_cur.device
-    if not ll_cur.is_cuda or ll_cur.dtype != torch.float64 or tuple(ll_cur.shape) != (C,) or \
-            not ll_cur.is_contiguous():
-        raise ValueError(f"{what}: ll_cur: a contiguous float64 GPU tensor [{C}] expected")
-    if any(t.device != dev for t in (ll_cur, chol_in, prior, h_start, obs)):
-        raise ValueError(f"{what}: all tensors on one device expected")
-    key, row = ctypes.c_uint64(seed & (2 ** 64 - 1)), ctypes.c_uint64(int(row0))
-    out = _adaptive_outputs(C, n_iter, P, trace, dev)
-    d = _lib.PmmhDesc(_lib.MODEL_SV, C, N, n_iter, it0, T_total, float(dt), 0.0)
-    check(_lib.load().vissm_sv_pmmh_adaptive(ctypes.byref(d), key, row, ptr(theta_cur), ptr(ll_cur), ptr(chol_in),
-                                             ptr(prior), ptr(h_start), ptr(obs), adapt_end, target_accept, gamma,
-                                             *[ptr(t) for t in out], _lib.stream_handle(dev)),
-          "vissm_sv_pmmh_adaptive")
-    return _adaptive_result(out)
+    return _pmmh_chain("sv_pmmh_adaptive", True, _lib.MODEL_SV, theta_cur, ll_cur, chol_in, prior, h_start, obs, None,
+                       dt, 0.0, N, n_iter, seed, row0, it0, trace, (adapt_end, target_accept, gamma))
