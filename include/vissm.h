@@ -944,6 +944,71 @@ int vissm_sv_pmmh_adaptive(const VissmPmmhDesc* d, uint64_t seed, uint64_t row0,
                            float* chol_trace /* [C][n_iter][4][4] or NULL */, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Correlated pseudo-marginal Metropolis-Hastings for the stochastic-volatility model (Deligiannidis, Doucet & Pitt
+ * 2018; csrc/cpm_math.hpp, csrc/sv_sorted.hip).  The chain carries the filter's random numbers as part of its state,
+ * proposes them by u' = rho u + sqrt(1 - rho^2) eps and resamples in sorted order, so that the noise of ll' - ll falls
+ * by an order of magnitude at the same N; it still targets p(theta | y) exactly.
+ *
+ * The auxiliary state of one filter of N particles over T = T_total steps, G = ceil(T / 4):
+ *   aux_n [G][N][4] fp32  the move normals: entry (t, j) at group t / 4, slot j, word t % 4 (16-byte aligned; the tail
+ *                         words of the last group are written 0 and never read)
+ *   aux_r [T] fp32        the resampling normals
+ *
+ * vissm_sv_filter_sorted: K filters, VissmPfDesc with model = VISSM_MODEL_SV, t0 = 0 and H = T_total (anything else is
+ * refused; there is no chaining in time), geometry and N as vissm_sv_filter.  theta [K][4], x_start [K N], obs
+ * [T + 1], aux_n [K][G][N][4], aux_r [K][T].  Step ta:
+ *   the N pre-step states are sorted ascending by key(h) = bits ^ 0x80000000 (sign clear) or ~bits (sign set), anything
+ *   not finite 0xFFFFFFFF: position j holds h_(j), -0 before +0, dead particles (the quiet NaN) last;
+ *   logw_j of h_(j), m, q_j, W, ll_inc, tau_j and anc[j] as in vissm_sv_filter, with
+ *   U = min(2^24 - 1, floor(Phi(aux_r[ta]) 2^24)), Phi(x) = erfc(-x / sqrt 2) / 2 in double;
+ *   position j takes h_(anc[j]) and moves it with the normal aux_n(ta, j).
+ * W = 0 kills the filter (loglik = -inf, NaN after).  loglik [K] double, ll_inc [K][T].  Optional traces for tests,
+ * NULL in production: cloud [K][T][N] (h after the move, in slot order), sorted_trace [K][T][N] (the pre-step states as
+ * sorted), q_trace [K][T][N] uint64, anc_trace [K][T][N] int32, u_trace [K][T] uint32.  No random numbers are drawn, no
+ * atomics: bitwise reproducible, and filter k's bits depend on (theta_k, its aux, N, y) only.
+ * vissm_sv_filter_sorted_lds_bytes: 8 N + 4 N + 192 + (N > 64: 8 N for the sort's exchanges, else 4); 0 = bad N.
+ *
+ * vissm_sv_cpmmh: vissm_sv_pmmh_adaptive's chains (adapt_end = 0: fixed proposals from chol_in) around that filter.
+ * A chain owns two halves of aux, aux_n [C][2][G][N][4] and aux_r [C][2][T]; aux_sel [C] int32 (0 or 1) says which half
+ * belongs to the chain's current state (theta_cur, ll_cur).  All three are read and written.  Iteration i of chain c,
+ * r = row0 + (i C + c) N:
+ *   theta', lp', log u and the decision with its -inf and NaN cases are vissm_sv_pmmh's (counter word 2 of row r);
+ *   un'(ta, j) = cn(un(ta, j), eps), eps the normal vissm_sv_pmmh's lane j consumes at step ta (row r + j, entry ta,
+ *   counter word 0);  ur'(ta) = cn(ur(ta), eps_r), eps_r the first Box-Muller output of the Philox block
+ *   (ta, 1, lo32(r), hi32(r));  cn(u, e) = fl32(fl32(rho u) + fl32(sqrt(1 - rho^2) e)), the root rounded once from double;
+ *   the proposal's aux is written to the half aux_sel does not name;
+ *   ll' = vissm_sv_filter_sorted's loglik on (theta', every particle at h_start[0], un', ur'), bit for bit;
+ *   accept: theta, ll and lp are taken and aux_sel[c] ^= 1.  Nothing is copied.
+ * A filter that dies leaves the rest of its half unwritten; a dead proposal is always rejected.  Outputs, traces,
+ * the adaptation, chol_end and chaining (with the same aux tensors) are vissm_sv_pmmh_adaptive's.  Refused by host
+ * arithmetic: what that entry refuses, rho outside [0, 1) (a NaN is outside), a null or misaligned aux pointer.
+ * vissm_sv_cpmmh_lds_bytes: the filter's + 4 N + 256; 0 = bad N.
+ * ------------------------------------------------------------------------- */
+int32_t vissm_sv_filter_sorted_lds_bytes(int32_t N);
+int vissm_sv_filter_sorted(const VissmPfDesc* d, const float* theta /* [K][4] */, const float* x_start /* [K N] */,
+                           const float* obs /* [T_total + 1] */, const float* aux_n /* [K][G][N][4] */,
+                           const float* aux_r /* [K][T] */, double* loglik /* [K] */, float* ll_inc /* [K][T] */,
+                           float* cloud /* [K][T][N] or NULL */, float* sorted_trace /* [K][T][N] or NULL */,
+                           uint64_t* q_trace /* [K][T][N] or NULL */, int32_t* anc_trace /* [K][T][N] or NULL */,
+                           uint32_t* u_trace /* [K][T] or NULL */, void* stream);
+
+int32_t vissm_sv_cpmmh_lds_bytes(int32_t N);
+int vissm_sv_cpmmh(const VissmPmmhDesc* d, uint64_t seed, uint64_t row0,
+                   const float* theta_cur /* [C][4] */, const double* ll_cur /* [C] */,
+                   const float* chol_in /* [C][4][4] lower */, const float* prior /* [4][2] (mean, sd) */,
+                   const float* h_start /* [1] */, const float* obs /* y[0 .. T_total] */,
+                   int32_t adapt_end, double target_accept, double gamma, float rho,
+                   float* aux_n /* [C][2][G][N][4], in and out */, float* aux_r /* [C][2][T], in and out */,
+                   int32_t* aux_sel /* [C], in and out */,
+                   float* theta_chain /* [C][n_iter][4] */, double* ll_chain /* [C][n_iter] */,
+                   int32_t* accept /* [C][n_iter] */, float* theta_end /* [C][4] */, double* ll_end /* [C] */,
+                   float* chol_end /* [C][4][4] */,
+                   float* theta_prop /* [C][n_iter][4] or NULL */, double* ll_prop /* [C][n_iter] or NULL */,
+                   double* logu /* [C][n_iter] or NULL */, float* xi_trace /* [C][n_iter][8] or NULL */,
+                   double* alpha_trace /* [C][n_iter] or NULL */, double* eta_trace /* [C][n_iter] or NULL */,
+                   float* chol_trace /* [C][n_iter][4][4] or NULL */, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Opt-in kernel timing (for bench.py's live roofline): when enabled, the flow
  * entry points bracket their main kernel with hipEvents on the launch stream.
  * kind: VISSM_PROF_FLOW_FWD / VISSM_PROF_FLOW_BWD (flow kernels),

@@ -238,6 +238,12 @@ SIGNATURES = {
                                [_i32, ctypes.c_double, ctypes.c_double] + [_c_void_p] * 13 + [_c_void_p]),
     "vissm_sv_smooth": (_i32, [ctypes.POINTER(PsDesc), _u64, _u64] + [_c_void_p] * 3 + [_i32] + [_c_void_p] * 5 +
                         [_c_void_p]),
+    "vissm_sv_filter_sorted_lds_bytes": (_i32, [_i32]),
+    "vissm_sv_filter_sorted": (_i32, [ctypes.POINTER(PfDesc)] + [_c_void_p] * 12 + [_c_void_p]),
+    "vissm_sv_cpmmh_lds_bytes": (_i32, [_i32]),
+    "vissm_sv_cpmmh": (_i32, [ctypes.POINTER(PmmhDesc), _u64, _u64] + [_c_void_p] * 6 +
+                       [_i32, ctypes.c_double, ctypes.c_double, ctypes.c_float] + [_c_void_p] * 3 +
+                       [_c_void_p] * 13 + [_c_void_p]),
     "vissm_profile_enable": (None, [_i32]),
     "vissm_profile_read": (_i32, [_i32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_i64)]),
     "vissm_profile_reset": (None, []),

@@ -7,6 +7,7 @@
 // of gp_math.hpp (the adapted filter's predictive weight and conditional draw) against numpy.linalg in float64,
 // of svf_math.hpp (the stochastic-volatility filter's weight and move, the smoother's pair weight) against float64,
 // of mh_math.hpp (the Metropolis-Hastings chain's words, proposal, log-prior and acceptance rule) against numpy,
+// of cpm_math.hpp (the correlated chain's move of a carried normal, sort key and resampling integer) against numpy,
 // and one whole iteration of the stochastic-volatility chain, run serially on mh_math.hpp and svf_math.hpp.
 // Not part of the product path: libvissm_hostcheck.so is loaded only by tests/.
 #include <cstddef>
@@ -21,6 +22,7 @@
 #include "gp_math.hpp"
 #include "svf_math.hpp"
 #include "mh_math.hpp"
+#include "cpm_math.hpp"
 
 extern "C" {
 
@@ -301,6 +303,17 @@ int hc_mh_adapt(float* L, const float* xi, double alpha, double eta, double targ
   double work[vissm::mh::adapt_work(vissm::mh::kMaxP)];
   return vissm::mh::adapt(L, xi, alpha, eta, target, P, work) ? 1 : 0;
 }
+
+// The correlated chain's shared math (cpm_math.hpp: the code sv_filter_sorted_kernel and sv_cpmmh_kernel run).
+// hc_cpm_cn: the autoregressive move of one carried normal; hc_cpm_sigma: sqrt(1 - rho^2) as the entry rounds it;
+// hc_cpm_valid_rho: the entry's refusal; hc_cpm_sort_key / hc_cpm_key_value: the sort key and its inverse;
+// hc_cpm_resample_u: the 24-bit resampling integer of a carried normal.
+float hc_cpm_cn(float u, float eps, float rho, float sigma) { return vissm::cpm::cn(u, eps, rho, sigma); }
+float hc_cpm_sigma(float rho) { return vissm::cpm::sigma_of(rho); }
+int hc_cpm_valid_rho(float rho) { return vissm::cpm::valid_rho(rho) ? 1 : 0; }
+uint32_t hc_cpm_sort_key(float h) { return vissm::cpm::sort_key(h); }
+float hc_cpm_key_value(uint32_t k) { return vissm::cpm::key_value(k); }
+uint32_t hc_cpm_resample_u(float ur) { return vissm::cpm::resample_u(ur); }
 
 // One iteration of one stochastic-volatility chain (sv_pmmh_kernel's, pmmh.hip) run serially on mh_math.hpp and
 // svf::filter_step: iteration i of chain c of C with n particles from the state theta [4] with the estimate ll_cur.

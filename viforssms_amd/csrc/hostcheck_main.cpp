@@ -87,6 +87,12 @@ int hc_mh_accept(double logu, double ll_prop, double ll_cur, double lp_prop, dou
 double hc_mh_alpha(double ll_prop, double ll_cur, double lp_prop, double lp_cur);
 double hc_mh_eta(int P, int64_t i, double gamma);
 int hc_mh_adapt(float* L, const float* xi, double alpha, double eta, double target, int P);
+float hc_cpm_cn(float u, float eps, float rho, float sigma);
+float hc_cpm_sigma(float rho);
+int hc_cpm_valid_rho(float rho);
+uint32_t hc_cpm_sort_key(float h);
+float hc_cpm_key_value(uint32_t k);
+uint32_t hc_cpm_resample_u(float ur);
 int hc_svpmmh_iteration(uint64_t seed, uint64_t row0, uint64_t i, uint64_t C, uint64_t c, int n, int T, float dt,
                         const float* theta, double ll_cur, const float* L, const float* prior, float h_start,
                         const float* y, float* theta_prop, double* out, float* h_tr, uint64_t* q_tr, int32_t* anc_tr,
@@ -1007,6 +1013,52 @@ int check_svpmmh() {
   return bad;
 }
 
+// cpm_math.hpp: cn is rho u + sigma eps with each product rounded on its own; sigma^2 + rho^2 = 1; the sort key's
+// unsigned order is the numeric order with -0 before +0 and everything not finite last, key_value inverts it; the
+// resampling integer is monotone, clamped at both ends and half of 2^24 at 0
+int check_cpm() {
+  int bad = 0;
+  for (float rho : {0.f, 0.5f, 0.9f, 0.99f, 0.999f, 0.9999f}) {
+    const float s = hc_cpm_sigma(rho);
+    if (std::fabs(static_cast<double>(s) * s + static_cast<double>(rho) * rho - 1.0) > 2e-7 || !hc_cpm_valid_rho(rho)) {
+      std::printf("cpm: sigma(%g) = %g\n", rho, s);
+      ++bad;
+    }
+    for (int i = 0; i < 200; ++i) {
+      const float u = static_cast<float>(uniform(-4.0, 4.0)), e = static_cast<float>(uniform(-4.0, 4.0));
+      volatile float a = rho * u, b = s * e;
+      const float want = a + b, got = hc_cpm_cn(u, e, rho, s);
+      if (std::memcmp(&want, &got, sizeof want) != 0) { std::printf("cpm: cn(%g, %g)\n", u, e); ++bad; }
+    }
+  }
+  if (hc_cpm_valid_rho(1.f) || hc_cpm_valid_rho(-0.1f) || hc_cpm_valid_rho(NAN)) { std::printf("cpm: rho\n"); ++bad; }
+  const float inf = INFINITY;
+  const float asc[] = {-3.4e38f, -8.5f, -1e-40f, -0.f, 0.f, 1e-40f, 1.f, 3.4e38f};
+  for (size_t i = 0; i < sizeof asc / sizeof asc[0]; ++i) {
+    const uint32_t k = hc_cpm_sort_key(asc[i]);
+    const float back = hc_cpm_key_value(k);
+    if (std::memcmp(&back, &asc[i], sizeof back) != 0) { std::printf("cpm: key_value(key(%g))\n", asc[i]); ++bad; }
+    if (i && !(hc_cpm_sort_key(asc[i - 1]) < k)) { std::printf("cpm: key order at %g\n", asc[i]); ++bad; }
+    if (k == 0xFFFFFFFFu) { std::printf("cpm: a finite value has the dead key\n"); ++bad; }
+  }
+  for (float v : {inf, -inf, NAN, -NAN}) {
+    if (hc_cpm_sort_key(v) != 0xFFFFFFFFu) { std::printf("cpm: key of %g\n", v); ++bad; }
+  }
+  if (!std::isnan(hc_cpm_key_value(0xFFFFFFFFu))) { std::printf("cpm: the dead key's value\n"); ++bad; }
+  if (hc_cpm_resample_u(0.f) != (1u << 23) || hc_cpm_resample_u(-40.f) != 0u || hc_cpm_resample_u(40.f) != 16777215u ||
+      hc_cpm_resample_u(8.f) != 16777215u || hc_cpm_resample_u(-inf) != 0u || hc_cpm_resample_u(inf) != 16777215u) {
+    std::printf("cpm: resample_u ends\n");
+    ++bad;
+  }
+  uint32_t last = 0;
+  for (int i = -800; i <= 800; ++i) {
+    const uint32_t U = hc_cpm_resample_u(0.01f * i);
+    if (U < last || U > 16777215u) { std::printf("cpm: resample_u(%g) = %u\n", 0.01 * i, U); ++bad; }
+    last = U;
+  }
+  return bad;
+}
+
 }  // namespace
 
 int main() {
@@ -1036,6 +1088,7 @@ int main() {
   bad += check_mh();
   bad += check_mh_adapt();
   bad += check_svpmmh();
+  bad += check_cpm();
   bad += check_colkey();
   bad += check_select();
   for (int which = 0; which < 9; ++which) {

@@ -29,6 +29,9 @@ MCMC_SEED_XOR = 0x3C3C7E7A
 # Measured at N = 1024 and 64 chains: 3.1 us per AR step, 0.81 s per launch at T = 5000;
 # volatility_mcmc() (section 4.13): 4.3 us per SV step, 1.12 s per launch at T = 1508
 MCMC_LAUNCH_STEPS = 1 << 18
+# xor-ed into the chains' Philox key for the fresh carried normals of the correlated chain (ops.cpm_fresh_aux): their
+# rows start at the iterations' base, under a key of their own
+CPM_SEED_XOR = 0x436F72724E6F6973
 # device bytes of the filter's cloud [K N, S, T] fp32 that particle_smoother() may keep for its backward pass
 SMOOTH_CLOUD_BYTES = 8 << 30
 # device bytes one forecast launch may write per output ([B, S, chunk] fp32): the default chunk is the largest
@@ -286,7 +289,7 @@ class PosteriorDiagnostics:
     @torch.no_grad()
     def theta_mcmc(self, n_chains: int = 64, n_particles: int = 256, n_iter: int = 2000, burn_in: int = 500,
                    step_scale: float = 1.0, probs=DEFAULT_PROBS, adapt: bool = False, target_accept: float = 0.234,
-                   adapt_decay: float = 0.5) -> Dict[str, np.ndarray]:
+                   adapt_decay: float = 0.5, correlation: float = 0.0) -> Dict[str, np.ndarray]:
         """The posterior p(theta | y) to lay over q(theta): C = n_chains particle marginal Metropolis-Hastings chains
         (ops.pmmh; Andrieu, Doucet & Holenstein 2010) whose acceptance ratio holds the fully adapted filter's unbiased
         estimate of p(y | theta) from N = n_particles particles, so they target p(theta | y) exactly for any N.  The
@@ -315,9 +318,15 @@ class PosteriorDiagnostics:
         chain, which targets p(theta | y) exactly.  The launches are cut as before and chained through chol_end as
         well.  The result gains mcmc/prop_chol_end [C, P, P], the chains' frozen factors, and mcmc/accept_rate_adapt
         [C], the acceptance over the adaptation; mcmc/prop_chol stays the starting factor.  burn_in = 0,
-        target_accept outside (0, 1) or adapt_decay outside (0, 1]: ValueError.  With adapt = False nothing changes."""
+        target_accept outside (0, 1) or adapt_decay outside (0, 1]: ValueError.  With adapt = False nothing changes.
+
+        correlation: the correlated pseudo-marginal chain is built for SV only (volatility_mcmc(); a one-dimensional
+        state sorts by value, LV and FHN would need a space-filling order): anything but 0.0 is a ValueError."""
         from . import ops
         md = self.mdef
+        if float(correlation) != 0.0:
+            raise ValueError(f"theta_mcmc: correlation={correlation}: the correlated chain is not built for AR, LV and "
+                             "FHN (volatility_mcmc() has it for SV)")
         if md.model_id == _lib.MODEL_SV or getattr(self, "filter_data", None) is None:
             raise ValueError("theta_mcmc: SV has no observation model (its first coordinate is the observed series)")
         C, N, n_iter, burn, p = self._mcmc_args("theta_mcmc", n_chains, n_particles, n_iter, burn_in, step_scale, probs)
@@ -431,16 +440,18 @@ class PosteriorDiagnostics:
 
     def save_theta_mcmc(self, PATH: str, n_chains: int = 64, n_particles: int = 256, n_iter: int = 2000,
                         burn_in: int = 500, step_scale: float = 1.0, probs=DEFAULT_PROBS, adapt: bool = False,
-                        target_accept: float = 0.234, adapt_decay: float = 0.5) -> Dict[str, np.ndarray]:
+                        target_accept: float = 0.234, adapt_decay: float = 0.5,
+                        correlation: float = 0.0) -> Dict[str, np.ndarray]:
         """theta_mcmc written as one .npz by rank 0 (every rank computes the same result)."""
         return self._save_npz(PATH, self.theta_mcmc(n_chains, n_particles, n_iter, burn_in, step_scale, probs, adapt,
-                                                    target_accept, adapt_decay))
+                                                    target_accept, adapt_decay, correlation))
 
     # ------------------------------------------------------------------ the theta posterior of the SV family
     @torch.no_grad()
     def volatility_mcmc(self, n_chains: int = 64, n_particles: int = 256, n_iter: int = 2000, burn_in: int = 500,
                         step_scale: float = 1.0, probs=DEFAULT_PROBS, adapt: bool = False,
-                        target_accept: float = 0.234, adapt_decay: float = 0.5) -> Dict[str, np.ndarray]:
+                        target_accept: float = 0.234, adapt_decay: float = 0.5,
+                        correlation: float = 0.0) -> Dict[str, np.ndarray]:
         """theta_mcmc() for the SV family, which theta_mcmc() refuses: the same chains (ops.sv_pmmh) around
         volatility_filter()'s filter, which is exactly fully adapted.  The data and its refusals are that method's: the
         observed series y[0 .. T], every particle started at x0; ValueError for a family other than SV, a y[0 .. T]
@@ -448,9 +459,20 @@ class PosteriorDiagnostics:
         4) Sigma_q, the start at samples 0 .. C - 1 of the broadcast draw, the Philox key seed ^ MCMC_SEED_XOR, the rows
         based at global_step C N (n_iter + 1) (the initial estimates, ops.sv_filter(cloud=False), take the first C N),
         the launches of max(1, MCMC_LAUNCH_STEPS // T) iterations and every returned key are theta_mcmc()'s, and so
-        are adapt, target_accept and adapt_decay (ops.sv_pmmh_adaptive) with the two keys they add."""
+        are adapt, target_accept and adapt_decay (ops.sv_pmmh_adaptive) with the two keys they add.
+
+        correlation = rho in (0, 0.9999]: the correlated pseudo-marginal chain (ops.sv_cpmmh; Deligiannidis, Doucet &
+        Pitt 2018).  Each chain carries its filter's normals (ops.cpm_fresh_aux under the key seed ^ MCMC_SEED_XOR ^
+        CPM_SEED_XOR, rows from the same base), proposes them by u' = rho u + sqrt(1 - rho^2) eps and resamples in
+        sorted order (ops.sv_filter_sorted gives the initial estimates), which takes most of the estimate's noise out of
+        the acceptance ratio at the same N; the chain still targets p(theta | y) exactly.  The launches are cut as
+        before, the carried normals persisting across them; adapt composes.  The result gains mcmc/correlation.  0.0
+        takes the path above unchanged; anything else is a ValueError."""
         from . import ops
         md = self.mdef
+        rho = float(correlation)
+        if not 0.0 <= rho <= 0.9999:
+            raise ValueError(f"volatility_mcmc: correlation={correlation} outside [0, 0.9999]")
         if md.model_id != _lib.MODEL_SV:
             raise ValueError(f"volatility_mcmc: the {md.family} family has an observation model: theta_mcmc() is its "
                              "check; this one is SV's")
@@ -467,9 +489,22 @@ class PosteriorDiagnostics:
         seed = self.engine.seed ^ MCMC_SEED_XOR
         row0 = self.global_step * C * N * (n_iter + 1)
         th = draw[:C].contiguous()
-        ll = ops.sv_filter(th, h0, obs, md.dt, N, seed, row0, cloud=False).loglik
         per = max(1, MCMC_LAUNCH_STEPS // max(T, 1))
         runs = []
+        if rho > 0.0:
+            aux_n, aux_r, aux_sel = ops.cpm_fresh_aux(C, T, N, seed ^ CPM_SEED_XOR, row0, dev)
+            ll = ops.sv_filter_sorted(th, h0, obs, md.dt, N, aux_n[:, 0].contiguous(),
+                                      aux_r[:, 0].contiguous()).loglik
+            Lc = L.repeat(C, 1, 1)
+            for it0 in range(0, n_iter, per):
+                r = ops.sv_cpmmh(th, ll, Lc, prior, h0, obs, md.dt, N, min(per, n_iter - it0), seed, row0 + C * N, rho,
+                                 aux_n, aux_r, aux_sel, burn if adapt else 0, target_accept, adapt_decay, it0=it0)
+                th, ll, Lc = r.theta_end, r.ll_end, r.chol_end
+                runs.append(r)
+            res = self._mcmc_result(runs, burn, p, probs, chol, draw, Lc if adapt else None)
+            res["mcmc/correlation"] = np.float64(rho)
+            return res
+        ll = ops.sv_filter(th, h0, obs, md.dt, N, seed, row0, cloud=False).loglik
         Lc = L.repeat(C, 1, 1) if adapt else None
         for it0 in range(0, n_iter, per):
             if adapt:
@@ -485,10 +520,11 @@ class PosteriorDiagnostics:
 
     def save_volatility_mcmc(self, PATH: str, n_chains: int = 64, n_particles: int = 256, n_iter: int = 2000,
                              burn_in: int = 500, step_scale: float = 1.0, probs=DEFAULT_PROBS, adapt: bool = False,
-                             target_accept: float = 0.234, adapt_decay: float = 0.5) -> Dict[str, np.ndarray]:
+                             target_accept: float = 0.234, adapt_decay: float = 0.5,
+                             correlation: float = 0.0) -> Dict[str, np.ndarray]:
         """volatility_mcmc written as one .npz by rank 0 (every rank computes the same result)."""
         return self._save_npz(PATH, self.volatility_mcmc(n_chains, n_particles, n_iter, burn_in, step_scale, probs,
-                                                         adapt, target_accept, adapt_decay))
+                                                         adapt, target_accept, adapt_decay, correlation))
 
     # ------------------------------------------------------------------ particle smoother
     @torch.no_grad()

@@ -1443,3 +1443,171 @@ def sv_pmmh_adaptive(theta_cur: torch.Tensor, ll_cur: torch.Tensor, chol_in: tor
     pmmh_adaptive's."""
     return _pmmh_chain("sv_pmmh_adaptive", True, _lib.MODEL_SV, theta_cur, ll_cur, chol_in, prior, h_start, obs, None,
                        dt, 0.0, N, n_iter, seed, row0, it0, trace, (adapt_end, target_accept, gamma))
+
+
+# ---------------------------------------------------------------------------------------
+# correlated pseudo-marginal chain of the stochastic-volatility model (sorted filter, carried noise)
+# ---------------------------------------------------------------------------------------
+@dataclass
+class SortedFilterResult:
+    loglik: torch.Tensor                    # [K] float64 (-inf: a dead filter)
+    ll_inc: torch.Tensor                    # [K, T] fp32 (NaN from the step a filter died at)
+    cloud: Optional[torch.Tensor]           # [K, T, N] h after the move, in slot order, or None
+    sorted_trace: Optional[torch.Tensor]    # [K, T, N] the pre-step states as sorted, or None
+    q_trace: Optional[torch.Tensor]         # [K, T, N] int64 the integer weights of the sorted states, or None
+    anc_trace: Optional[torch.Tensor]       # [K, T, N] int32 positions in the sorted array, or None
+    u_trace: Optional[torch.Tensor]         # [K, T] int32 the resampling integers (below 2^24), or None
+
+
+@dataclass
+class CpmmhResult(PmmhAdaptiveResult):
+    aux_sel: torch.Tensor = None            # [C] int32: the tensor passed in, after the launch
+
+
+def cpm_groups(T: int) -> int:
+    """G = ceil(T / 4): the Philox groups of a row of T move normals."""
+    return (int(T) + 3) // 4
+
+
+def _cpm_aux(fn: str, aux_n, aux_r, lead: tuple, T: int, N: int, dev):
+    G = cpm_groups(T)
+    for name, t, shape in (("aux_n", aux_n, lead + (G, N, 4)), ("aux_r", aux_r, lead + (T,))):
+        if not t.is_cuda or t.device != dev or t.dtype != torch.float32 or tuple(t.shape) != shape or \
+                not t.is_contiguous():
+            raise ValueError(f"{fn}: {name}: a contiguous fp32 tensor {list(shape)} on theta's device expected, got "
+                             f"{t.dtype} {tuple(t.shape)}")
+
+
+def sv_filter_sorted(theta: torch.Tensor, x_start: torch.Tensor, obs: torch.Tensor, dt: float, N: int,
+                     aux_n: torch.Tensor, aux_r: torch.Tensor, cloud: bool = False,
+                     trace: bool = False) -> SortedFilterResult:
+    """K particle filters of the stochastic-volatility model over the whole series obs = y[0 .. T], all randomness
+    given: aux_n [K, G, N, 4] holds the move normals (entry (t, j) at [k, t // 4, j, t % 4], G = ceil(T / 4)) and
+    aux_r [K, T] the resampling normals; vissm_sv_filter_sorted.  Each step sorts the pre-step states ascending (dead
+    particles last), weighs, resamples with U = floor(Phi(aux_r[t]) 2^24) and moves position j's ancestor with
+    aux_n(t, j): sv_filter's filter with a sort before the scan, so that nearby aux give nearby estimates.  x_start:
+    [K N] or one value.  cloud: also h after each move [K, T, N]; trace: also the sorted states, the integer weights,
+    the ancestors and U.  Nothing is drawn: two calls are bitwise equal."""
+    N = int(N)
+    if N not in _lib.PF_PARTICLES:
+        raise ValueError(f"sv_filter_sorted: N={N} particles, one of {_lib.PF_PARTICLES} expected")
+    if not 0.0 < float(dt) < float("inf"):
+        raise ValueError(f"sv_filter_sorted: dt must be positive and finite, got {dt}")
+    _require_gpu(theta, x_start)
+    if theta.dtype != torch.float32 or x_start.dtype != torch.float32 or theta.dim() != 2 or theta.shape[1] != 4:
+        raise ValueError(f"sv_filter_sorted: fp32 theta [K, 4] and x_start expected, got {tuple(theta.shape)}")
+    K, dev = theta.shape[0], theta.device
+    if K * N >= 2 ** 31:
+        raise ValueError(f"sv_filter_sorted: K N = {K} * {N} reaches 2^31")
+    if x_start.numel() == 1:
+        x_start = x_start.reshape(1).expand(K * N).contiguous()
+    if x_start.numel() != K * N or x_start.device != dev:
+        raise ValueError(f"sv_filter_sorted: x_start [{K * N}] (or one value) on theta's device expected, got "
+                         f"{tuple(x_start.shape)}")
+    T = _sv_series("sv_filter_sorted", obs, dev)
+    if T < 1:
+        raise ValueError("sv_filter_sorted: a series of at least one transition expected")
+    _cpm_aux("sv_filter_sorted", aux_n, aux_r, (K,), T, N, dev)
+    e = lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, device=dev)
+    loglik, ll_inc = e(K, dtype=torch.float64), e(K, T)
+    cl = e(K, T, N) if cloud else None
+    st = e(K, T, N) if trace else None
+    qt = e(K, T, N, dtype=torch.int64) if trace else None
+    at = e(K, T, N, dtype=torch.int32) if trace else None
+    ut = e(K, T, dtype=torch.int32) if trace else None
+    res = SortedFilterResult(loglik, ll_inc, cl, st, qt, at, ut)
+    if K == 0:
+        return res
+    d = _lib.PfDesc(_lib.MODEL_SV, K, N, T, 0, T, float(dt), 0.0)
+    check(_lib.load().vissm_sv_filter_sorted(ctypes.byref(d), ptr(theta), ptr(x_start), ptr(obs), ptr(aux_n),
+                                             ptr(aux_r), ptr(loglik), ptr(ll_inc), ptr(cl), ptr(st), ptr(qt), ptr(at),
+                                             ptr(ut), _lib.stream_handle(dev)), "vissm_sv_filter_sorted")
+    return res
+
+
+def cpm_fresh_aux(C: int, T: int, N: int, seed: int, row0: int, device="cuda"):
+    """A fresh auxiliary state for sv_cpmmh: (aux_n [C, 2, G, N, 4], aux_r [C, 2, T], aux_sel [C] int32).  Half 0 holds
+    independent N(0, 1) values -- the move normal (t, j) of chain c is entry t of row row0 + c N + j of
+    normal_base(seed, ...), its resampling normal t entry t of row row0 + C N + c -- half 1 and aux_sel are zero.  The
+    ll_cur that goes with it is sv_filter_sorted(theta_cur, h_start, obs, dt, N, aux_n[:, 0], aux_r[:, 0]).loglik."""
+    C, T, N = int(C), int(T), int(N)
+    if C < 1 or T < 1 or N not in _lib.PF_PARTICLES:
+        raise ValueError(f"cpm_fresh_aux: C={C} (>= 1), T={T} (>= 1), N={N} (one of {_lib.PF_PARTICLES}) expected")
+    if not 0 <= int(row0) < 2 ** 64 - C * (N + 1):
+        raise ValueError(f"cpm_fresh_aux: row0={row0} outside [0, 2^64 - C (N + 1))")
+    G = cpm_groups(T)
+    dev = torch.device(device)
+    eps, _ = normal_base(seed, int(row0), C * N, T, 1, dev)
+    aux_n = torch.zeros(C, 2, G, N, 4, dtype=torch.float32, device=dev)
+    pad = torch.zeros(C, N, 4 * G, dtype=torch.float32, device=dev)
+    pad[:, :, :T] = eps.view(C, N, T)
+    aux_n[:, 0] = pad.view(C, N, G, 4).permute(0, 2, 1, 3)
+    aux_r = torch.zeros(C, 2, T, dtype=torch.float32, device=dev)
+    aux_r[:, 0] = normal_base(seed, int(row0) + C * N, C, T, 1, dev)[0]
+    return aux_n, aux_r, torch.zeros(C, dtype=torch.int32, device=dev)
+
+
+def sv_cpmmh(theta_cur: torch.Tensor, ll_cur: torch.Tensor, chol_in: torch.Tensor, prior: torch.Tensor,
+             h_start: torch.Tensor, obs: torch.Tensor, dt: float, N: int, n_iter: int, seed: int, row0: int,
+             rho: float, aux_n: torch.Tensor, aux_r: torch.Tensor, aux_sel: torch.Tensor, adapt_end: int = 0,
+             target_accept: float = 0.234, gamma: float = 0.5, it0: int = 0, trace: bool = False) -> CpmmhResult:
+    """sv_pmmh_adaptive as a correlated pseudo-marginal chain (vissm_sv_cpmmh; Deligiannidis, Doucet & Pitt 2018): the
+    chain carries its filter's random numbers, proposes them by u' = rho u + sqrt(1 - rho^2) eps and estimates
+    log p(y | theta') with sv_filter_sorted on the proposed numbers, so the noise of ll' - ll is far below the
+    independent filter's at the same N.  aux_n [C, 2, G, N, 4], aux_r [C, 2, T] and aux_sel [C] int32 (cpm_fresh_aux)
+    are MUTATED IN PLACE: the half aux_sel[c] names belongs to (theta_cur[c], ll_cur[c]) -- ll_cur must be
+    sv_filter_sorted's estimate on that half -- the proposal is written to the other half and acceptance flips
+    aux_sel[c].  eps are the normals sv_pmmh's filter would consume in the same iteration (rows row0 + (i C + c) N + j).
+    adapt_end = 0 is the fixed-proposal chain with the factors chol_in [C, 4, 4].  A call with it0' = it0 + n_iter,
+    theta_end, ll_end, chol_end and the same three aux tensors continues bitwise.  Every other argument, the outputs
+    and the traces are sv_pmmh_adaptive's; the result also holds aux_sel (the same tensor)."""
+    what, P = "sv_cpmmh", 4
+    N, n_iter, it0, rho = int(N), int(n_iter), int(it0), float(rho)
+    if N not in _lib.PF_PARTICLES:
+        raise ValueError(f"{what}: N={N} particles, one of {_lib.PF_PARTICLES} expected")
+    if not 0.0 < float(dt) < float("inf"):
+        raise ValueError(f"{what}: dt must be positive and finite, got {dt}")
+    if not 0.0 <= rho < 1.0 or not 0.0 <= float(torch.tensor(rho, dtype=torch.float32)) < 1.0:
+        raise ValueError(f"{what}: rho={rho} outside [0, 1) (as an fp32 value)")
+    if theta_cur.dim() != 2 or theta_cur.shape[1] != P or theta_cur.shape[0] < 1:
+        raise ValueError(f"{what}: theta_cur [C >= 1, {P}] expected, got {tuple(theta_cur.shape)}")
+    C = theta_cur.shape[0]
+    if n_iter < 0 or it0 < 0 or it0 + n_iter >= 2 ** 31:
+        raise ValueError(f"{what}: bad iterations it0={it0} n_iter={n_iter}")
+    adapt = _adaptive_args(what, adapt_end, target_accept, gamma)
+    if not 0 <= int(row0) < 2 ** 64:
+        raise ValueError(f"{what}: row0={row0} outside [0, 2^64)")
+    _require_gpu(theta_cur, chol_in, prior, h_start, obs)
+    dev = theta_cur.device
+    T = _sv_series(what, obs, dev)
+    if T < 1 or T >= 2 ** 31 - 1:
+        raise ValueError(f"{what}: T = {T}: at least one transition, fewer than 2^31 - 1 expected")
+    for name, x, shape in (("theta_cur", theta_cur, (C, P)), ("chol_in", chol_in, (C, P, P)), ("prior", prior, (P, 2)),
+                           ("h_start", h_start, (1,))):
+        if x.dtype != torch.float32 or tuple(x.shape) != shape or x.device != dev:
+            raise ValueError(f"{what}: fp32 {name} {list(shape)} on one device expected, got {x.dtype} "
+                             f"{tuple(x.shape)}")
+    if not ll_cur.is_cuda or ll_cur.dtype != torch.float64 or tuple(ll_cur.shape) != (C,) or \
+            not ll_cur.is_contiguous() or ll_cur.device != dev:
+        raise ValueError(f"{what}: ll_cur: a contiguous float64 GPU tensor [{C}] expected")
+    _cpm_aux(what, aux_n, aux_r, (C, 2), T, N, dev)
+    if not aux_sel.is_cuda or aux_sel.device != dev or aux_sel.dtype != torch.int32 or \
+            tuple(aux_sel.shape) != (C,) or not aux_sel.is_contiguous():
+        raise ValueError(f"{what}: aux_sel: a contiguous int32 GPU tensor [{C}] expected")
+    if bool(((aux_sel != 0) & (aux_sel != 1)).any()):
+        raise ValueError(f"{what}: aux_sel holds a value other than 0 and 1")
+    key, row = ctypes.c_uint64(seed & (2 ** 64 - 1)), ctypes.c_uint64(int(row0))
+    f32, f64 = torch.float32, torch.float64
+    e = lambda *shape, dtype=f32: torch.empty(*shape, dtype=dtype, device=dev)
+    t = lambda *shape, dtype=f32: e(*shape, dtype=dtype) if trace else None
+    chain = [e(C, n_iter, P), e(C, n_iter, dtype=f64), e(C, n_iter, dtype=torch.int32), e(C, P), e(C, dtype=f64)]
+    traces = [t(C, n_iter, P), t(C, n_iter, dtype=f64), t(C, n_iter, dtype=f64)]
+    chol_end = e(C, P, P)
+    more = [t(C, n_iter, 8), t(C, n_iter, dtype=f64), t(C, n_iter, dtype=f64), t(C, n_iter, P, P)]
+    d = _lib.PmmhDesc(_lib.MODEL_SV, C, N, n_iter, it0, T, float(dt), 0.0)
+    check(_lib.load().vissm_sv_cpmmh(ctypes.byref(d), key, row, *map(ptr, (theta_cur, ll_cur, chol_in, prior, h_start,
+                                                                             obs)), *adapt, ctypes.c_float(rho),
+                                     ptr(aux_n), ptr(aux_r), ptr(aux_sel),
+                                     *map(ptr, chain + [chol_end] + traces + more), _lib.stream_handle(dev)),
+          "vissm_sv_cpmmh")
+    return CpmmhResult(*chain, *traces, chol_end, *more, aux_sel)

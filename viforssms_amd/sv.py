@@ -85,9 +85,18 @@ def run(argv=None):
                          "iterations (robust adaptive Metropolis towards 23.4 %% acceptance) and keeps it frozen over "
                          "the second half, which is kept; also written: the chains' final factors and their acceptance "
                          "while adapting")
+    ap.add_argument("--mcmc-corr", type=float, metavar="RHO", default=0.0,
+                    help="With --mcmc: the correlated pseudo-marginal chain -- each chain carries its filter's random "
+                         "numbers, proposes them by u' = RHO u + sqrt(1 - RHO^2) eps (0 < RHO <= 0.9999; 0.99 is a "
+                         "good start) and resamples in sorted order, which takes most of the estimate's noise out of the "
+                         "acceptance ratio at the same N; composes with --mcmc-adapt")
     args = ap.parse_args(argv)
     if args.mcmc_adapt and args.mcmc is None:
         ap.error("--mcmc-adapt applies to --mcmc: give it")
+    if args.mcmc_corr != 0.0 and args.mcmc is None:
+        ap.error("--mcmc-corr applies to --mcmc: give it")
+    if not 0.0 <= args.mcmc_corr <= 0.9999:
+        ap.error("--mcmc-corr: RHO in (0, 0.9999] expected (0: the ordinary chain)")
     for name, n_int in (("filter", 2), ("smooth", 3), ("mcmc", 3)):
         v = getattr(args, name)
         if v is not None:
@@ -121,5 +130,6 @@ def run(argv=None):
         # a quarter of the iterations is burn-in, as the default's; with --mcmc-adapt the chains adapt their proposals
         # over the first half and the second half is kept
         model.save_volatility_mcmc(args.mcmc[3], args.mcmc[0], args.mcmc[1], args.mcmc[2],
-                                   burn_in=args.mcmc[2] // (2 if args.mcmc_adapt else 4), adapt=args.mcmc_adapt)
+                                   burn_in=args.mcmc[2] // (2 if args.mcmc_adapt else 4), adapt=args.mcmc_adapt,
+                                   correlation=args.mcmc_corr)
     return model
