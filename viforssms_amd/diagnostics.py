@@ -211,65 +211,87 @@ class PosteriorDiagnostics:
         post-propagation particles (n_valid leaves out the LV particles that left the orthant after a resampling).
         With the default every launch and every entry is the bootstrap filter's, with no new key.  Any other value:
         VissmError."""
-        return self._filter_pass(n_theta, n_particles, probs, chunk, None, proposal)[0]
+        return self._filter_pass("particle_filter", n_theta, n_particles, None, probs, chunk, proposal)
 
-    def _filter_pass(self, n_theta, n_particles, probs, chunk, keep, proposal="bootstrap"):
-        """particle_filter()'s launches and result; with keep = (M, cap) the arguments of particle_smoother() are
-        checked before the first launch and every chunk's cloud stays on the device: (res, theta, [(t0, cloud)])."""
+    def _filter_pass(self, what, n_theta, n_particles, n_paths, probs, chunk, proposal):
+        """particle_filter() and particle_smoother() (`what`; n_paths None for the filter): their own refusals, then
+        _filter_smooth() on the model's observations from its x0 with ops.particle_filter / ops.particle_smooth."""
         from . import ops
         md = self.mdef
-        what = "particle_filter" if keep is None else "particle_smoother"
         if proposal not in ops.PF_PROPOSALS:
             raise _lib.VissmError(f"{what}: proposal {proposal!r}, one of {ops.PF_PROPOSALS} expected")
         if md.model_id == _lib.MODEL_SV or getattr(self, "filter_data", None) is None:
             raise ValueError(f"{what}: SV has no observation model (its first coordinate is the observed "
                              "series)")
+
+        def data():
+            dev = self.engine.device
+            obs_h, bin_h, x0_h = self.filter_data
+            T = min(int(self.target_len()), obs_h.shape[1])
+            obs = torch.as_tensor(np.ascontiguousarray(obs_h[:, :T]), device=dev)
+            obs_bin = torch.as_tensor(np.ascontiguousarray(bin_h[:, :T]), device=dev)
+            step = lambda th, state, N, seed, row0, **kw: ops.particle_filter(
+                md.model_id, th, state, obs, obs_bin, md.dt, md.obs_std, N, seed, row0, cloud=True, proposal=proposal,
+                **kw)
+            smooth = lambda th, cloud, M, seed, row0, **kw: ops.particle_smooth(md.model_id, th, cloud, md.dt, M, seed,
+                                                                                row0, **kw)
+            return T, torch.as_tensor(x0_h, device=dev), step, smooth
+
+        # the sizes' refusals carry particle_filter's name for the smoother too
+        return self._filter_smooth(what, "particle_filter", _lib.MODEL_S[md.model_id], data, n_theta, n_particles,
+                                   n_paths, probs, chunk, proposal)
+
+    def _broadcast_rank0(self, t: torch.Tensor) -> torch.Tensor:
+        """t overwritten on every rank with rank 0's (one process: t as it is)."""
+        if self.dist.world > 1:
+            import torch.distributed as dist
+            dist.broadcast(t, src=dist.get_global_rank(self.dist.group, 0) if self.dist.group is not None else 0,
+                           group=self.dist.group)
+        return t
+
+    def _filter_smooth(self, what, label, S, data, n_theta, n_particles, n_paths, probs, chunk, proposal):
+        """The launches and the result of the two filters (n_paths None) and the two smoothers, for the public method
+        `what`; `label` is the name its refusals of n_particles, n_theta and chunk carry, S the filtered state's
+        coordinates, proposal what filter/proposal reports ("bootstrap": no such entry).  data(), called once those
+        sizes are checked, raises the refusals of the data and returns (T, state, step, smooth): the steps, the start
+        state and the two ops calls, step(th, state, N, seed, row0, t0=, loglik_in=, H=) and smooth(th, cloud, M, seed,
+        row0, t0=, x_next=).  A smoother's n_paths, T and cloud bytes are checked before the first launch, and every
+        chunk's cloud then stays on the device until the backward pass has smoothed it."""
         K, N = int(n_theta), int(n_particles)
         if N not in _lib.PF_PARTICLES:
-            raise ValueError(f"particle_filter: n_particles={N}, one of {_lib.PF_PARTICLES} expected")
+            raise ValueError(f"{label}: n_particles={N}, one of {_lib.PF_PARTICLES} expected")
         if not 1 <= K <= self.p_local:
-            raise ValueError(f"particle_filter: n_theta={K} outside 1 .. p_local = {self.p_local}")
+            raise ValueError(f"{label}: n_theta={K} outside 1 .. p_local = {self.p_local}")
         p = _check_probs(probs)
         chunk = self.filter_chunk(K, N) if chunk is None else int(chunk)
         if chunk < 1:
-            raise ValueError(f"particle_filter chunk {chunk} < 1")
-        dev = self.engine.device
-        S, Q = _lib.MODEL_S[md.model_id], p.size
-        obs_h, bin_h, x0_h = self.filter_data
-        T = min(int(self.target_len()), obs_h.shape[1])
-        if keep is not None:
-            M, cap = keep
+            raise ValueError(f"{label} chunk {chunk} < 1")
+        T, state, step, smooth = data()
+        if n_paths is not None:
+            M, cap = int(n_paths), SMOOTH_CLOUD_BYTES
             if not (_lib.PS_MIN_PATHS <= M <= N and M & (M - 1) == 0):
-                raise ValueError(f"particle_smoother: n_paths={M}, a power of two in {_lib.PS_MIN_PATHS} .. "
-                                 f"n_particles = {N} expected")
+                raise ValueError(f"{what}: n_paths={M}, a power of two in {_lib.PS_MIN_PATHS} .. n_particles = {N} "
+                                 "expected")
             if T < 1:
-                raise ValueError("particle_smoother: no step to smooth")
+                raise ValueError(f"{what}: no step to smooth")
             if 4 * K * N * S * T > cap:
-                raise ValueError(f"particle_smoother: the filter's cloud [{K} * {N}, {S}, {T}] fp32 takes "
-                                 f"{4 * K * N * S * T} bytes, more than SMOOTH_CLOUD_BYTES = {cap}: lower n_theta or "
-                                 "n_particles")
-        obs = torch.as_tensor(np.ascontiguousarray(obs_h[:, :T]), device=dev)
-        obs_bin = torch.as_tensor(np.ascontiguousarray(bin_h[:, :T]), device=dev)
-        x0 = torch.as_tensor(x0_h, device=dev)
+                raise ValueError(f"{what}: the filter's cloud [{K} * {N}, {S}, {T}] fp32 takes {4 * K * N * S * T} "
+                                 f"bytes, more than SMOOTH_CLOUD_BYTES = {cap}: lower n_theta or n_particles")
+        dev = self.engine.device
+        Q = p.size
         _, theta = self.sample_paths_theta(np.tile(0, self.p_local), step=self.global_step)
-        th = theta.detach().float()[:K].contiguous()
-        if self.dist.world > 1:
-            import torch.distributed as dist
-            dist.broadcast(th, src=dist.get_global_rank(self.dist.group, 0) if self.dist.group is not None else 0,
-                           group=self.dist.group)
-        seed = self.engine.seed ^ FILTER_SEED_XOR
+        th = self._broadcast_rank0(theta.detach().float()[:K].contiguous())
         row0 = self.global_step * K * N
-        state, ll = x0, None
+        ll = None
         incs, esss, parts, clouds = [], [], [], []
         for t0 in range(0, T, chunk):
             m = min(chunk, T - t0)
-            r = ops.particle_filter(md.model_id, th, state, obs, obs_bin, md.dt, md.obs_std, N, seed, row0, t0=t0,
-                                    loglik_in=ll, cloud=True, H=m, proposal=proposal)
+            r = step(th, state, N, self.engine.seed ^ FILTER_SEED_XOR, row0, t0=t0, loglik_in=ll, H=m)
             state, ll = r.state_end, r.loglik
             incs.append(r.ll_inc)
             esss.append(r.ess)
             parts.append((m, column_summary(r.cloud.view(K * N, S * m), probs, None)))
-            if keep is not None:
+            if n_paths is not None:
                 clouds.append((t0, r.cloud))
         res: Dict[str, np.ndarray] = {"probs": p, "filter/theta": th.cpu().numpy()}
         if proposal != "bootstrap":
@@ -278,7 +300,17 @@ class PosteriorDiagnostics:
         res["filter/ll_inc"] = torch.cat(incs + [torch.zeros(K, 0, device=dev)], 1).cpu().numpy()
         res["filter/ess"] = torch.cat(esss + [torch.zeros(K, 0, device=dev)], 1).cpu().numpy()
         res.update(stack_bands("filter", parts, S, Q))
-        return res, th, clouds
+        parts, x_next = [], None
+        while clouds:
+            t0, cloud = clouds.pop()          # last chunk first; the cloud is freed once it is smoothed
+            r = smooth(th, cloud, M, self.engine.seed ^ SMOOTH_SEED_XOR, row0, t0=t0, x_next=x_next)
+            x_next = r.x_first
+            m = cloud.shape[2]
+            parts.append((m, column_summary(r.paths.view(K * M, S * m), probs, None)))
+            del cloud, r
+        if n_paths is not None:
+            res.update(stack_bands("smooth", parts[::-1], S, Q))
+        return res
 
     def save_filter(self, PATH: str, n_theta: int = 64, n_particles: int = 1024, probs=DEFAULT_PROBS,
                     chunk: Optional[int] = None, proposal: str = "bootstrap") -> Dict[str, np.ndarray]:
@@ -345,21 +377,30 @@ class PosteriorDiagnostics:
         th = draw[:C].contiguous()
         ll = ops.particle_filter(md.model_id, th, x0, obs, obs_bin, md.dt, md.obs_std, N, seed, row0, cloud=False,
                                  proposal="adapted").loglik
+        if adapt:
+            def step(it0, n, th, ll, Lc):
+                r = ops.pmmh_adaptive(md.model_id, th, ll, Lc, prior, x0, obs, obs_bin, md.dt, md.obs_std, N, n, seed,
+                                      row0 + C * N, burn, target_accept, adapt_decay, it0=it0)
+                return r, (r.theta_end, r.ll_end, r.chol_end)
+        else:
+            def step(it0, n, th, ll):
+                r = ops.pmmh(md.model_id, th, ll, L, prior, x0, obs, obs_bin, md.dt, md.obs_std, N, n, seed,
+                             row0 + C * N, it0=it0)
+                return r, (r.theta_end, r.ll_end)
+        runs, end = self._mcmc_launches(n_iter, T, (th, ll) + ((L.repeat(C, 1, 1),) if adapt else ()), step)
+        return self._mcmc_result(runs, burn, p, probs, chol, draw, end[2] if adapt else None)
+
+    @staticmethod
+    def _mcmc_launches(n_iter, T, state, step):
+        """The run of theta_mcmc() / volatility_mcmc() cut into launches of max(1, MCMC_LAUNCH_STEPS // T) iterations:
+        step(it0, n, *state) runs iterations it0 .. it0 + n - 1 and returns (its result, the state the next launch
+        takes: theta_end, ll_end and, where the chains carry their factors, chol_end).  ([results], the last state)."""
         per = max(1, MCMC_LAUNCH_STEPS // max(T, 1))
         runs = []
-        Lc = L.repeat(C, 1, 1) if adapt else None
         for it0 in range(0, n_iter, per):
-            if adapt:
-                r = ops.pmmh_adaptive(md.model_id, th, ll, Lc, prior, x0, obs, obs_bin, md.dt, md.obs_std, N,
-                                      min(per, n_iter - it0), seed, row0 + C * N, burn, target_accept, adapt_decay,
-                                      it0=it0)
-                Lc = r.chol_end
-            else:
-                r = ops.pmmh(md.model_id, th, ll, L, prior, x0, obs, obs_bin, md.dt, md.obs_std, N,
-                             min(per, n_iter - it0), seed, row0 + C * N, it0=it0)
-            th, ll = r.theta_end, r.ll_end
+            r, state = step(it0, min(per, n_iter - it0), *state)
             runs.append(r)
-        return self._mcmc_result(runs, burn, p, probs, chol, draw, Lc)
+        return runs, state
 
     def _mcmc_args(self, what, n_chains, n_particles, n_iter, burn_in, step_scale, probs):
         """The checks theta_mcmc() and volatility_mcmc() share: (C, N, n_iter, burn, p)."""
@@ -392,11 +433,7 @@ class PosteriorDiagnostics:
         the model's prior [P, 2]: (draw, chol, L, prior)."""
         dev = self.engine.device
         _, theta = self.sample_paths_theta(np.tile(0, self.p_local), step=self.global_step)
-        draw = theta.detach().float().contiguous()
-        if self.dist.world > 1:
-            import torch.distributed as dist
-            dist.broadcast(draw, src=dist.get_global_rank(self.dist.group, 0) if self.dist.group is not None else 0,
-                           group=self.dist.group)
+        draw = self._broadcast_rank0(theta.detach().float().contiguous())
         sigma = np.atleast_2d(np.cov(draw.cpu().numpy().astype(np.float64).T))
         try:
             if not np.isfinite(sigma).all():
@@ -489,34 +526,32 @@ class PosteriorDiagnostics:
         seed = self.engine.seed ^ MCMC_SEED_XOR
         row0 = self.global_step * C * N * (n_iter + 1)
         th = draw[:C].contiguous()
-        per = max(1, MCMC_LAUNCH_STEPS // max(T, 1))
-        runs = []
         if rho > 0.0:
             aux_n, aux_r, aux_sel = ops.cpm_fresh_aux(C, T, N, seed ^ CPM_SEED_XOR, row0, dev)
             ll = ops.sv_filter_sorted(th, h0, obs, md.dt, N, aux_n[:, 0].contiguous(),
                                       aux_r[:, 0].contiguous()).loglik
-            Lc = L.repeat(C, 1, 1)
-            for it0 in range(0, n_iter, per):
-                r = ops.sv_cpmmh(th, ll, Lc, prior, h0, obs, md.dt, N, min(per, n_iter - it0), seed, row0 + C * N, rho,
-                                 aux_n, aux_r, aux_sel, burn if adapt else 0, target_accept, adapt_decay, it0=it0)
-                th, ll, Lc = r.theta_end, r.ll_end, r.chol_end
-                runs.append(r)
-            res = self._mcmc_result(runs, burn, p, probs, chol, draw, Lc if adapt else None)
-            res["mcmc/correlation"] = np.float64(rho)
-            return res
-        ll = ops.sv_filter(th, h0, obs, md.dt, N, seed, row0, cloud=False).loglik
-        Lc = L.repeat(C, 1, 1) if adapt else None
-        for it0 in range(0, n_iter, per):
+
+            def step(it0, n, th, ll, Lc):
+                r = ops.sv_cpmmh(th, ll, Lc, prior, h0, obs, md.dt, N, n, seed, row0 + C * N, rho, aux_n, aux_r,
+                                 aux_sel, burn if adapt else 0, target_accept, adapt_decay, it0=it0)
+                return r, (r.theta_end, r.ll_end, r.chol_end)
+        else:
+            ll = ops.sv_filter(th, h0, obs, md.dt, N, seed, row0, cloud=False).loglik
             if adapt:
-                r = ops.sv_pmmh_adaptive(th, ll, Lc, prior, h0, obs, md.dt, N, min(per, n_iter - it0), seed,
-                                         row0 + C * N, burn, target_accept, adapt_decay, it0=it0)
-                Lc = r.chol_end
+                def step(it0, n, th, ll, Lc):
+                    r = ops.sv_pmmh_adaptive(th, ll, Lc, prior, h0, obs, md.dt, N, n, seed, row0 + C * N, burn,
+                                             target_accept, adapt_decay, it0=it0)
+                    return r, (r.theta_end, r.ll_end, r.chol_end)
             else:
-                r = ops.sv_pmmh(th, ll, L, prior, h0, obs, md.dt, N, min(per, n_iter - it0), seed, row0 + C * N,
-                                it0=it0)
-            th, ll = r.theta_end, r.ll_end
-            runs.append(r)
-        return self._mcmc_result(runs, burn, p, probs, chol, draw, Lc)
+                def step(it0, n, th, ll):
+                    r = ops.sv_pmmh(th, ll, L, prior, h0, obs, md.dt, N, n, seed, row0 + C * N, it0=it0)
+                    return r, (r.theta_end, r.ll_end)
+        carried = rho > 0.0 or adapt                 # these chains hold a factor each
+        runs, end = self._mcmc_launches(n_iter, T, (th, ll) + ((L.repeat(C, 1, 1),) if carried else ()), step)
+        res = self._mcmc_result(runs, burn, p, probs, chol, draw, end[2] if adapt else None)
+        if rho > 0.0:
+            res["mcmc/correlation"] = np.float64(rho)
+        return res
 
     def save_volatility_mcmc(self, PATH: str, n_chains: int = 64, n_particles: int = 256, n_iter: int = 2000,
                              burn_in: int = 500, step_scale: float = 1.0, probs=DEFAULT_PROBS, adapt: bool = False,
@@ -547,23 +582,7 @@ class PosteriorDiagnostics:
 
         proposal = "adapted": the forward pass is particle_filter(proposal="adapted")'s, whose cloud is, like the
         bootstrap's, an equally weighted sample of each filtering law; the backward pass is untouched."""
-        from . import ops
-        md = self.mdef
-        K, N, M = int(n_theta), int(n_particles), int(n_paths)
-        res, th, clouds = self._filter_pass(K, N, probs, chunk, (M, SMOOTH_CLOUD_BYTES), proposal)
-        S, Q = _lib.MODEL_S[md.model_id], res["probs"].size
-        seed = self.engine.seed ^ SMOOTH_SEED_XOR
-        row0 = self.global_step * K * N
-        parts, x_next = [], None
-        while clouds:
-            t0, cloud = clouds.pop()          # last chunk first; the cloud is freed once it is smoothed
-            r = ops.particle_smooth(md.model_id, th, cloud, md.dt, M, seed, row0, t0=t0, x_next=x_next)
-            x_next = r.x_first
-            m = cloud.shape[2]
-            parts.append((m, column_summary(r.paths.view(K * M, S * m), probs, None)))
-            del cloud, r
-        res.update(stack_bands("smooth", parts[::-1], S, Q))
-        return res
+        return self._filter_pass("particle_smoother", n_theta, n_particles, int(n_paths), probs, chunk, proposal)
 
     def save_smoother(self, PATH: str, n_theta: int = 64, n_particles: int = 1024, n_paths: int = 64,
                       probs=DEFAULT_PROBS, chunk: Optional[int] = None,
@@ -587,66 +606,27 @@ class PosteriorDiagnostics:
         filter/{mean, sd, n_valid, quantiles} summarises the K N equally weighted particles of p(h_t+1 | y_0:t+1).
         ValueError before any launch: a family other than SV, a y[0 .. T] that is not finite, a y[0 .. T - 1] equal
         to 0 (the density degenerates)."""
-        return self._volatility_pass(n_theta, n_particles, probs, chunk, None)[0]
+        return self._volatility_pass("volatility_filter", n_theta, n_particles, None, probs, chunk)
 
-    def _volatility_pass(self, n_theta, n_particles, probs, chunk, keep):
-        """volatility_filter()'s launches and result; with keep = (M, cap) the arguments of volatility_smoother() are
-        checked before the first launch and every chunk's cloud stays on the device: (res, theta, obs, [(t0, cloud)])."""
+    def _volatility_pass(self, what, n_theta, n_particles, n_paths, probs, chunk):
+        """volatility_filter() and volatility_smoother() (`what`; n_paths None for the filter): their own refusal, then
+        _filter_smooth() on the observed series from h_0 = x0 with ops.sv_filter / ops.sv_smooth."""
         from . import ops
         md = self.mdef
-        what = "volatility_filter" if keep is None else "volatility_smoother"
         if md.model_id != _lib.MODEL_SV:
             raise ValueError(f"{what}: the {md.family} family has an observation model: particle_filter() and "
                              "particle_smoother() are its checks; this one is SV's")
-        K, N = int(n_theta), int(n_particles)
-        if N not in _lib.PF_PARTICLES:
-            raise ValueError(f"{what}: n_particles={N}, one of {_lib.PF_PARTICLES} expected")
-        if not 1 <= K <= self.p_local:
-            raise ValueError(f"{what}: n_theta={K} outside 1 .. p_local = {self.p_local}")
-        p = _check_probs(probs)
-        chunk = self.filter_chunk(K, N) if chunk is None else int(chunk)
-        if chunk < 1:
-            raise ValueError(f"{what} chunk {chunk} < 1")
-        y_h, T = self._volatility_series(what)
-        if keep is not None:
-            M, cap = keep
-            if not (_lib.PS_MIN_PATHS <= M <= N and M & (M - 1) == 0):
-                raise ValueError(f"{what}: n_paths={M}, a power of two in {_lib.PS_MIN_PATHS} .. n_particles = {N} "
-                                 "expected")
-            if T < 1:
-                raise ValueError(f"{what}: no step to smooth")
-            if 4 * K * N * T > cap:
-                raise ValueError(f"{what}: the filter's cloud [{K} * {N}, 1, {T}] fp32 takes {4 * K * N * T} bytes, "
-                                 f"more than SMOOTH_CLOUD_BYTES = {cap}: lower n_theta or n_particles")
-        dev = self.engine.device
-        Q = p.size
-        obs = torch.as_tensor(y_h, device=dev)
-        _, theta = self.sample_paths_theta(np.tile(0, self.p_local), step=self.global_step)
-        th = theta.detach().float()[:K].contiguous()
-        if self.dist.world > 1:
-            import torch.distributed as dist
-            dist.broadcast(th, src=dist.get_global_rank(self.dist.group, 0) if self.dist.group is not None else 0,
-                           group=self.dist.group)
-        seed = self.engine.seed ^ FILTER_SEED_XOR
-        row0 = self.global_step * K * N
-        state, ll = torch.full((1,), float(self.x0), dtype=torch.float32, device=dev), None
-        incs, esss, parts, clouds = [], [], [], []
-        for t0 in range(0, T, chunk):
-            m = min(chunk, T - t0)
-            r = ops.sv_filter(th, state, obs, md.dt, N, seed, row0, t0=t0, loglik_in=ll, cloud=True, H=m)
-            state, ll = r.state_end, r.loglik
-            incs.append(r.ll_inc)
-            esss.append(r.ess)
-            parts.append((m, column_summary(r.cloud.view(K * N, m), probs, None)))
-            if keep is not None:
-                clouds.append((t0, r.cloud))
-        res: Dict[str, np.ndarray] = {"probs": p, "filter/theta": th.cpu().numpy(),
-                                      "filter/proposal": np.asarray("adapted")}
-        res["filter/loglik"] = ll.cpu().numpy() if ll is not None else np.zeros(K)
-        res["filter/ll_inc"] = torch.cat(incs + [torch.zeros(K, 0, device=dev)], 1).cpu().numpy()
-        res["filter/ess"] = torch.cat(esss + [torch.zeros(K, 0, device=dev)], 1).cpu().numpy()
-        res.update(stack_bands("filter", parts, 1, Q))
-        return res, th, obs, clouds
+
+        def data():
+            y_h, T = self._volatility_series(what)
+            dev = self.engine.device
+            obs = torch.as_tensor(y_h, device=dev)
+            step = lambda th, state, N, seed, row0, **kw: ops.sv_filter(th, state, obs, md.dt, N, seed, row0,
+                                                                        cloud=True, **kw)
+            smooth = lambda th, cloud, M, seed, row0, **kw: ops.sv_smooth(th, cloud, obs, md.dt, M, seed, row0, **kw)
+            return T, torch.full((1,), float(self.x0), dtype=torch.float32, device=dev), step, smooth
+
+        return self._filter_smooth(what, what, 1, data, n_theta, n_particles, n_paths, probs, chunk, "adapted")
 
     def _volatility_series(self, what):
         """The observed series y[0 .. T] fp32 the SV filter reads and T, refused where it is not finite or a y[0 .. T - 1]
@@ -676,23 +656,7 @@ class PosteriorDiagnostics:
         n_valid} [1, T] and smooth/quantiles [Q, 1, T]: column t is p(h_t+1 | y_0:T) averaged over q(theta), to lay
         directly over paths/quantiles of posterior_summary().  `chunk` changes nothing; every rank runs the same
         launches and holds the same result.  Refusals as volatility_filter()."""
-        from . import ops
-        md = self.mdef
-        K, N, M = int(n_theta), int(n_particles), int(n_paths)
-        res, th, obs, clouds = self._volatility_pass(K, N, probs, chunk, (M, SMOOTH_CLOUD_BYTES))
-        Q = res["probs"].size
-        seed = self.engine.seed ^ SMOOTH_SEED_XOR
-        row0 = self.global_step * K * N
-        parts, x_next = [], None
-        while clouds:
-            t0, cloud = clouds.pop()          # last chunk first; the cloud is freed once it is smoothed
-            r = ops.sv_smooth(th, cloud, obs, md.dt, M, seed, row0, t0=t0, x_next=x_next)
-            x_next = r.x_first
-            m = cloud.shape[2]
-            parts.append((m, column_summary(r.paths.view(K * M, m), probs, None)))
-            del cloud, r
-        res.update(stack_bands("smooth", parts[::-1], 1, Q))
-        return res
+        return self._volatility_pass("volatility_smoother", n_theta, n_particles, int(n_paths), probs, chunk)
 
     def save_volatility_smoother(self, PATH: str, n_theta: int = 64, n_particles: int = 1024, n_paths: int = 64,
                                  probs=DEFAULT_PROBS, chunk: Optional[int] = None) -> Dict[str, np.ndarray]:

@@ -945,11 +945,39 @@ def _model_dims(fn: str, model_id: int, sv_lacks: Optional[str] = None):
     return _lib.MODEL_S[model_id], _lib.MODEL_P[model_id]
 
 
-def _key_and_row(fn: str, seed: int, row0: int):
+def _key_and_row(fn: str, seed: int, row0: int, exc=_lib.VissmError):
     """The Philox key (seed, masked to 64 bits) and first row of a launch as the C ABI takes them."""
     if not 0 <= int(row0) < 2 ** 64:
-        raise _lib.VissmError(f"{fn}: row0={row0} outside [0, 2^64)")
+        raise exc(f"{fn}: row0={row0} outside [0, 2^64)")
     return ctypes.c_uint64(seed & (2 ** 64 - 1)), ctypes.c_uint64(int(row0))
+
+
+# The checks the particle wrappers share.  The filters and smoothers refuse with VissmError, the chains and the sorted
+# filter with ValueError, so each takes the caller's name and its exception class.
+def _check_particles(fn: str, exc, N) -> int:
+    N = int(N)
+    if N not in _lib.PF_PARTICLES:
+        raise exc(f"{fn}: N={N} particles, one of {_lib.PF_PARTICLES} expected")
+    return N
+
+
+def _check_positive(fn: str, exc, value, wanted: str):
+    """value (dt, obs_std) positive and finite; wanted: the message up to the value."""
+    if not 0.0 < float(value) < float("inf"):
+        raise exc(f"{fn}: {wanted}, got {value}")
+
+
+def _check_rows(fn: str, exc, K: int, N: int):
+    if K * N >= 2 ** 31:
+        raise exc(f"{fn}: K N = {K} * {N} reaches 2^31")
+
+
+def _check_layout(fn: str, exc, name: str, t: torch.Tensor, shape: tuple, dtype, dev=None):
+    """t (loglik_in, ll_cur, x_next, aux_sel): a contiguous GPU tensor of that shape and dtype, on dev where given."""
+    if not t.is_cuda or (dev is not None and t.device != dev) or t.dtype != dtype or tuple(t.shape) != shape or \
+            not t.is_contiguous():
+        kind = {torch.float64: "float64", torch.float32: "fp32", torch.int32: "int32"}[dtype]
+        raise exc(f"{fn}: {name}: a contiguous {kind} GPU tensor [{', '.join(map(str, shape))}] expected")
 
 
 # ---------------------------------------------------------------------------------------
@@ -1025,43 +1053,64 @@ def particle_filter(model_id: int, theta: torch.Tensor, x_start: torch.Tensor, o
     observed step a particle is weighted on the predictive p(y_t | x_t-1) before it moves, and after the resampling
     drawn from p(x_t | x_t-1, y_t) with its own normals.  Same rows, streams, outputs and chaining; a much lower
     variance of loglik where obs_std is small against the process noise.  obs_std > 0 and finite."""
+    fn = "particle_filter"
     if proposal not in PF_PROPOSALS:
-        raise _lib.VissmError(f"particle_filter: proposal {proposal!r}, one of {PF_PROPOSALS} expected")
-    if proposal == "adapted" and not 0.0 < float(obs_std) < float("inf"):
-        raise _lib.VissmError(f"particle_filter: the adapted proposal needs a positive, finite obs_std, got {obs_std}")
-    S, P = _model_dims("particle_filter", model_id, sv_lacks="observation model")
-    N = int(N)
-    if N not in _lib.PF_PARTICLES:
-        raise _lib.VissmError(f"particle_filter: N={N} particles, one of {_lib.PF_PARTICLES} expected")
-    _require_gpu(theta, x_start, obs, obs_bin)
-    for name, t in (("theta", theta), ("x_start", x_start), ("obs", obs), ("obs_bin", obs_bin)):
+        raise _lib.VissmError(f"{fn}: proposal {proposal!r}, one of {PF_PROPOSALS} expected")
+    if proposal == "adapted":
+        _check_positive(fn, _lib.VissmError, obs_std, "the adapted proposal needs a positive, finite obs_std")
+    S, _ = _model_dims(fn, model_id, sv_lacks="observation model")
+
+    def x_start_of(n, dev):
+        x = x_start.unsqueeze(0).expand(n, S).contiguous() if x_start.dim() == 1 and x_start.shape[0] == S else x_start
+        if x.dim() != 2 or tuple(x.shape) != (n, S):
+            raise _lib.VissmError(f"{fn}: x_start [{n}, {S}] or [{S}] expected, got {tuple(x.shape)}")
+        return x
+
+    def series_of(dev):
+        if obs.dim() != 2 or obs.shape[0] != S or obs_bin.shape != obs.shape:
+            raise _lib.VissmError(f"{fn}: obs and obs_bin [{S}, T] expected, got {tuple(obs.shape)} and "
+                                  f"{tuple(obs_bin.shape)}")
+        if any(t.device != dev for t in (x_start, obs, obs_bin)):
+            raise _lib.VissmError(f"{fn}: all tensors on one device expected")
+        T_total = obs.shape[1]
+        return (obs, obs_bin), T_total, f"{T_total} observations ((t0 + H) * {S} must stay below 2^31)"
+
+    entry = "vissm_particle_filter_adapted" if proposal == "adapted" else "vissm_particle_filter"
+    return _filter(fn, entry, model_id, S, theta, x_start, (("obs", obs), ("obs_bin", obs_bin)), x_start_of, series_of,
+                   dt, False, obs_std, N, seed, row0, t0, loglik_in, cloud, trace, H)
+
+
+def _filter(fn: str, entry: str, model_id: int, S: int, theta, x_start, up_front: tuple, x_start_of, series_of, dt,
+            need_dt: bool, obs_std: float, N, seed, row0, t0, loglik_in, cloud: bool, trace: bool,
+            H) -> ParticleFilterResult:
+    """particle_filter and sv_filter: fn is the function's name, entry its C entry, S the coordinates of the filtered
+    state.  What differs comes from the caller: up_front, the (name, tensor) pairs checked with theta and x_start
+    before any shape; x_start_of(K N, dev), the x_start the entry takes (broadcast, its shape checked);
+    series_of(dev), the checked series as (the tensors the entry takes after x_start, T_total, the horizon refusal's
+    words for it); need_dt, whether dt must be positive and finite; obs_std, the descriptor's (0.0 without one)."""
+    exc = _lib.VissmError
+    N = _check_particles(fn, exc, N)
+    if need_dt:
+        _check_positive(fn, exc, dt, "dt must be positive and finite")
+    checked = (("theta", theta), ("x_start", x_start)) + up_front
+    _require_gpu(*(t for _, t in checked))
+    for name, t in checked:
         if t.dtype != torch.float32:
-            raise _lib.VissmError(f"particle_filter: fp32 {name} expected, got {t.dtype}")
+            raise exc(f"{fn}: fp32 {name} expected, got {t.dtype}")
+    P = _lib.MODEL_P[model_id]
     if theta.dim() != 2 or theta.shape[1] != P:
-        raise _lib.VissmError(f"particle_filter: theta [K, {P}] expected, got {tuple(theta.shape)}")
-    K = theta.shape[0]
-    if K * N >= 2 ** 31:
-        raise _lib.VissmError(f"particle_filter: K N = {K} * {N} reaches 2^31")
-    if x_start.dim() == 1 and x_start.shape[0] == S:
-        x_start = x_start.unsqueeze(0).expand(K * N, S).contiguous()
-    if x_start.dim() != 2 or tuple(x_start.shape) != (K * N, S):
-        raise _lib.VissmError(f"particle_filter: x_start [{K * N}, {S}] or [{S}] expected, got {tuple(x_start.shape)}")
-    if obs.dim() != 2 or obs.shape[0] != S or obs_bin.shape != obs.shape:
-        raise _lib.VissmError(f"particle_filter: obs and obs_bin [{S}, T] expected, got {tuple(obs.shape)} and "
-                              f"{tuple(obs_bin.shape)}")
-    dev = theta.device
-    if any(t.device != dev for t in (x_start, obs, obs_bin)):
-        raise _lib.VissmError("particle_filter: all tensors on one device expected")
-    T_total, t0 = obs.shape[1], int(t0)
+        raise exc(f"{fn}: theta [K, {P}] expected, got {tuple(theta.shape)}")
+    K, dev = theta.shape[0], theta.device
+    _check_rows(fn, exc, K, N)
+    x_start = x_start_of(K * N, dev)
+    series, T_total, series_words = series_of(dev)
+    t0 = int(t0)
     H = T_total - t0 if H is None else int(H)
     if H < 0 or t0 < 0 or t0 + H > T_total or (t0 + H) * S >= 2 ** 31:
-        raise _lib.VissmError(f"particle_filter: bad horizon H={H} t0={t0} for {T_total} observations "
-                              f"((t0 + H) * {S} must stay below 2^31)")
-    key, row = _key_and_row("particle_filter", seed, row0)
+        raise exc(f"{fn}: bad horizon H={H} t0={t0} for {series_words}")
+    key, row = _key_and_row(fn, seed, row0)
     if loglik_in is not None:
-        if not loglik_in.is_cuda or loglik_in.device != dev or loglik_in.dtype != torch.float64 or \
-                tuple(loglik_in.shape) != (K,) or not loglik_in.is_contiguous():
-            raise _lib.VissmError(f"particle_filter: loglik_in: a contiguous float64 GPU tensor [{K}] expected")
+        _check_layout(fn, exc, "loglik_in", loglik_in, (K,), torch.float64, dev)
     loglik = torch.empty(K, dtype=torch.float64, device=dev)
     ll_inc = torch.empty(K, H, dtype=torch.float32, device=dev)
     ess = torch.empty(K, H, dtype=torch.float32, device=dev)
@@ -1069,14 +1118,14 @@ def particle_filter(model_id: int, theta: torch.Tensor, x_start: torch.Tensor, o
     cl = torch.empty(K * N, S, H, dtype=torch.float32, device=dev) if cloud else None
     qt = torch.empty(K, H, N, dtype=torch.int64, device=dev) if trace else None
     at = torch.empty(K, H, N, dtype=torch.int32, device=dev) if trace else None
+    res = ParticleFilterResult(loglik, ll_inc, ess, state_end, cl, qt, at)
     if K == 0:
-        return ParticleFilterResult(loglik, ll_inc, ess, state_end, cl, qt, at)
+        return res
     d = _lib.PfDesc(model_id, K, N, H, t0, T_total, float(dt), float(obs_std))
-    name = "vissm_particle_filter_adapted" if proposal == "adapted" else "vissm_particle_filter"
-    check(getattr(_lib.load(), name)(ctypes.byref(d), key, row, ptr(theta), ptr(x_start), ptr(obs), ptr(obs_bin),
-                                     ptr(loglik_in), ptr(loglik), ptr(ll_inc), ptr(ess), ptr(state_end), ptr(cl),
-                                     ptr(qt), ptr(at), _lib.stream_handle(dev)), name)
-    return ParticleFilterResult(loglik, ll_inc, ess, state_end, cl, qt, at)
+    check(getattr(_lib.load(), entry)(ctypes.byref(d), key, row, ptr(theta), ptr(x_start), *map(ptr, series),
+                                      ptr(loglik_in), ptr(loglik), ptr(ll_inc), ptr(ess), ptr(state_end), ptr(cl),
+                                      ptr(qt), ptr(at), _lib.stream_handle(dev)), entry)
+    return res
 
 
 # ---------------------------------------------------------------------------------------
@@ -1099,44 +1148,53 @@ def particle_smooth(model_id: int, theta: torch.Tensor, cloud: torch.Tensor, dt:
     row0 + k N + j under `seed` at counter (t0 + t, 2, row).  x_next [K M, S] is the target of the last step (None:
     a uniform draw over the live particles there); a call over the steps before with x_next = this call's x_first
     and its own t0 continues bitwise.  AR, LV and FHN; SV has no filter and is refused."""
-    S, P = _model_dims("particle_smooth", model_id, sv_lacks="particle filter")
+    S, _ = _model_dims("particle_smooth", model_id, sv_lacks="particle filter")
+    return _smooth("particle_smooth", "vissm_particle_smooth", model_id, S, theta, cloud, dt, False,
+                   lambda dev, H, t0: ((), True, " (H >= 1 and t0 + H below 2^31)"), M, seed, row0, t0, x_next, idx,
+                   trace)
+
+
+def _smooth(fn: str, entry: str, model_id: int, S: int, theta, cloud, dt, need_dt: bool, series_of, M, seed, row0, t0,
+            x_next, idx: bool, trace: bool) -> ParticleSmoothResult:
+    """particle_smooth and sv_smooth: fn is the function's name, entry its C entry, S the cloud's coordinates.  The
+    caller hands in need_dt, whether dt must be positive and finite, and series_of(dev, H, t0): (the arguments the
+    entry takes between cloud and x_next, whether the series reaches as far as these columns need, the horizon
+    refusal's words after H and t0)."""
+    exc = _lib.VissmError
     _require_gpu(theta, cloud)
     for name, t in (("theta", theta), ("cloud", cloud)):
         if t.dtype != torch.float32:
-            raise _lib.VissmError(f"particle_smooth: fp32 {name} expected, got {t.dtype}")
+            raise exc(f"{fn}: fp32 {name} expected, got {t.dtype}")
+    P = _lib.MODEL_P[model_id]
     if theta.dim() != 2 or theta.shape[1] != P or theta.shape[0] < 1:
-        raise _lib.VissmError(f"particle_smooth: theta [K >= 1, {P}] expected, got {tuple(theta.shape)}")
+        raise exc(f"{fn}: theta [K >= 1, {P}] expected, got {tuple(theta.shape)}")
+    if need_dt:
+        _check_positive(fn, exc, dt, "dt must be positive and finite")
     K, M = theta.shape[0], int(M)
     if cloud.dim() != 3 or cloud.shape[1] != S or cloud.shape[0] % K or not cloud.is_contiguous():
-        raise _lib.VissmError(f"particle_smooth: a contiguous cloud [{K} N, {S}, H] expected, got "
-                              f"{tuple(cloud.shape)}")
-    N, H, t0 = cloud.shape[0] // K, cloud.shape[2], int(t0)
-    if N not in _lib.PF_PARTICLES:
-        raise _lib.VissmError(f"particle_smooth: N={N} particles, one of {_lib.PF_PARTICLES} expected")
+        raise exc(f"{fn}: a contiguous cloud [{K} N, {S}, H] expected, got {tuple(cloud.shape)}")
+    N, H, t0 = _check_particles(fn, exc, cloud.shape[0] // K), cloud.shape[2], int(t0)
     if not (_lib.PS_MIN_PATHS <= M <= N and M & (M - 1) == 0):
-        raise _lib.VissmError(f"particle_smooth: M={M} trajectories, a power of two in {_lib.PS_MIN_PATHS} .. N = {N} "
-                              "expected")
+        raise exc(f"{fn}: M={M} trajectories, a power of two in {_lib.PS_MIN_PATHS} .. N = {N} expected")
     if K > 65535:
-        raise _lib.VissmError(f"particle_smooth: K={K} filters, at most 65535 per call")
-    if H < 1 or t0 < 0 or t0 + H >= 2 ** 31:
-        raise _lib.VissmError(f"particle_smooth: bad horizon H={H} t0={t0} (H >= 1 and t0 + H below 2^31)")
-    key, row = _key_and_row("particle_smooth", seed, row0)
+        raise exc(f"{fn}: K={K} filters, at most 65535 per call")
     dev = theta.device
     if cloud.device != dev:
-        raise _lib.VissmError("particle_smooth: all tensors on one device expected")
+        raise exc(f"{fn}: all tensors on one device expected")
+    series_args, reaches, horizon_words = series_of(dev, H, t0)
+    if H < 1 or t0 < 0 or t0 + H >= 2 ** 31 or not reaches:
+        raise exc(f"{fn}: bad horizon H={H} t0={t0}{horizon_words}")
+    key, row = _key_and_row(fn, seed, row0)
     theta = theta.contiguous()
     if x_next is not None:
-        if not x_next.is_cuda or x_next.device != dev or x_next.dtype != torch.float32 or \
-                tuple(x_next.shape) != (K * M, S) or not x_next.is_contiguous():
-            raise _lib.VissmError(f"particle_smooth: x_next: a contiguous fp32 GPU tensor [{K * M}, {S}] expected")
+        _check_layout(fn, exc, "x_next", x_next, (K * M, S), torch.float32, dev)
     paths = torch.empty(K * M, S, H, dtype=torch.float32, device=dev)
     x_first = torch.empty(K * M, S, dtype=torch.float32, device=dev)
     ix = torch.empty(K * M, H, dtype=torch.int32, device=dev) if idx else None
     qt = torch.empty(K, H, M, N, dtype=torch.int64, device=dev) if trace else None
     d = _lib.PsDesc(model_id, K, N, M, H, t0, float(dt))
-    check(_lib.load().vissm_particle_smooth(ctypes.byref(d), key, row, ptr(theta), ptr(cloud), ptr(x_next),
-                                            ptr(paths), ptr(x_first), ptr(ix), ptr(qt), _lib.stream_handle(dev)),
-          "vissm_particle_smooth")
+    check(getattr(_lib.load(), entry)(ctypes.byref(d), key, row, ptr(theta), ptr(cloud), *series_args, ptr(x_next),
+                                      ptr(paths), ptr(x_first), ptr(ix), ptr(qt), _lib.stream_handle(dev)), entry)
     return ParticleSmoothResult(paths, x_first, ix, qt)
 
 
@@ -1152,6 +1210,16 @@ def _sv_series(fn: str, obs: torch.Tensor, dev) -> int:
     return obs.shape[0] - 1
 
 
+def _sv_x_start(fn: str, exc, x_start: torch.Tensor, n: int, dev, max_dim: Optional[int] = None) -> torch.Tensor:
+    """h at the first step for n particles: one value is broadcast, anything else holds n values (in at most max_dim
+    dimensions where given) on theta's device."""
+    if x_start.numel() == 1:
+        x_start = x_start.reshape(1).expand(n).contiguous()
+    if x_start.numel() != n or (max_dim is not None and x_start.dim() > max_dim) or x_start.device != dev:
+        raise exc(f"{fn}: x_start [{n}] (or one value) on theta's device expected, got {tuple(x_start.shape)}")
+    return x_start
+
+
 def sv_filter(theta: torch.Tensor, x_start: torch.Tensor, obs: torch.Tensor, dt: float, N: int, seed: int, row0: int,
               t0: int = 0, loglik_in: Optional[torch.Tensor] = None, cloud: bool = True, H: Optional[int] = None,
               trace: bool = False) -> ParticleFilterResult:
@@ -1162,49 +1230,15 @@ def sv_filter(theta: torch.Tensor, x_start: torch.Tensor, obs: torch.Tensor, dt:
     fully adapted filter.  x_start: h at step t0, [K N], [K N, 1] or one value for every particle.  Cloud column t is
     an equally weighted sample of p(h_{t0+t+1} | y_{0 : t0+t+1}); shapes, traces and chaining as particle_filter
     with S = 1.  Particle (k, i) uses Philox row row0 + k N + i with AR's stream (n_stream = 1)."""
-    N = int(N)
-    if N not in _lib.PF_PARTICLES:
-        raise _lib.VissmError(f"sv_filter: N={N} particles, one of {_lib.PF_PARTICLES} expected")
-    if not 0.0 < float(dt) < float("inf"):
-        raise _lib.VissmError(f"sv_filter: dt must be positive and finite, got {dt}")
-    _require_gpu(theta, x_start)
-    P = _lib.MODEL_P[_lib.MODEL_SV]
-    for name, t in (("theta", theta), ("x_start", x_start)):
-        if t.dtype != torch.float32:
-            raise _lib.VissmError(f"sv_filter: fp32 {name} expected, got {t.dtype}")
-    if theta.dim() != 2 or theta.shape[1] != P:
-        raise _lib.VissmError(f"sv_filter: theta [K, {P}] expected, got {tuple(theta.shape)}")
-    K, dev = theta.shape[0], theta.device
-    if K * N >= 2 ** 31:
-        raise _lib.VissmError(f"sv_filter: K N = {K} * {N} reaches 2^31")
-    if x_start.numel() == 1:
-        x_start = x_start.reshape(1).expand(K * N).contiguous()
-    if x_start.numel() != K * N or x_start.dim() > 2 or x_start.device != dev:
-        raise _lib.VissmError(f"sv_filter: x_start [{K * N}] (or one value) on theta's device expected, got "
-                              f"{tuple(x_start.shape)}")
-    T_total, t0 = _sv_series("sv_filter", obs, dev), int(t0)
-    H = T_total - t0 if H is None else int(H)
-    if H < 0 or t0 < 0 or t0 + H > T_total or t0 + H >= 2 ** 31:
-        raise _lib.VissmError(f"sv_filter: bad horizon H={H} t0={t0} for a series of {T_total} transitions")
-    key, row = _key_and_row("sv_filter", seed, row0)
-    if loglik_in is not None:
-        if not loglik_in.is_cuda or loglik_in.device != dev or loglik_in.dtype != torch.float64 or \
-                tuple(loglik_in.shape) != (K,) or not loglik_in.is_contiguous():
-            raise _lib.VissmError(f"sv_filter: loglik_in: a contiguous float64 GPU tensor [{K}] expected")
-    loglik = torch.empty(K, dtype=torch.float64, device=dev)
-    ll_inc = torch.empty(K, H, dtype=torch.float32, device=dev)
-    ess = torch.empty(K, H, dtype=torch.float32, device=dev)
-    state_end = torch.empty(K * N, 1, dtype=torch.float32, device=dev)
-    cl = torch.empty(K * N, 1, H, dtype=torch.float32, device=dev) if cloud else None
-    qt = torch.empty(K, H, N, dtype=torch.int64, device=dev) if trace else None
-    at = torch.empty(K, H, N, dtype=torch.int32, device=dev) if trace else None
-    if K == 0:
-        return ParticleFilterResult(loglik, ll_inc, ess, state_end, cl, qt, at)
-    d = _lib.PfDesc(_lib.MODEL_SV, K, N, H, t0, T_total, float(dt), 0.0)
-    check(_lib.load().vissm_sv_filter(ctypes.byref(d), key, row, ptr(theta), ptr(x_start), ptr(obs), ptr(loglik_in),
-                                      ptr(loglik), ptr(ll_inc), ptr(ess), ptr(state_end), ptr(cl), ptr(qt), ptr(at),
-                                      _lib.stream_handle(dev)), "vissm_sv_filter")
-    return ParticleFilterResult(loglik, ll_inc, ess, state_end, cl, qt, at)
+    fn = "sv_filter"
+
+    def series_of(dev):
+        T_total = _sv_series(fn, obs, dev)
+        return (obs,), T_total, f"a series of {T_total} transitions"
+
+    return _filter(fn, "vissm_sv_filter", _lib.MODEL_SV, 1, theta, x_start, (),
+                   lambda n, dev: _sv_x_start(fn, _lib.VissmError, x_start, n, dev, max_dim=2), series_of, dt, True,
+                   0.0, N, seed, row0, t0, loglik_in, cloud, trace, H)
 
 
 def sv_smooth(theta: torch.Tensor, cloud: torch.Tensor, obs: torch.Tensor, dt: float, M: int, seed: int, row0: int,
@@ -1216,49 +1250,16 @@ def sv_smooth(theta: torch.Tensor, cloud: torch.Tensor, obs: torch.Tensor, dt: f
     times p(y[t0 + c + 2] | y[t0 + c + 1], h_i).  Selection words, x_next [K M, 1] / x_first chaining, the terminal
     rule (x_next None: a uniform draw over the live particles of the last column), idx and trace as particle_smooth.
     Every column with a next state needs y[t0 + c + 2]: t0 + H (+ 1 with x_next) <= T."""
-    P = _lib.MODEL_P[_lib.MODEL_SV]
-    _require_gpu(theta, cloud)
-    for name, t in (("theta", theta), ("cloud", cloud)):
-        if t.dtype != torch.float32:
-            raise _lib.VissmError(f"sv_smooth: fp32 {name} expected, got {t.dtype}")
-    if theta.dim() != 2 or theta.shape[1] != P or theta.shape[0] < 1:
-        raise _lib.VissmError(f"sv_smooth: theta [K >= 1, {P}] expected, got {tuple(theta.shape)}")
-    if not 0.0 < float(dt) < float("inf"):
-        raise _lib.VissmError(f"sv_smooth: dt must be positive and finite, got {dt}")
-    K, M = theta.shape[0], int(M)
-    if cloud.dim() != 3 or cloud.shape[1] != 1 or cloud.shape[0] % K:
-        raise _lib.VissmError(f"sv_smooth: a contiguous cloud [{K} N, 1, H] expected, got {tuple(cloud.shape)}")
-    N, H, t0 = cloud.shape[0] // K, cloud.shape[2], int(t0)
-    if N not in _lib.PF_PARTICLES:
-        raise _lib.VissmError(f"sv_smooth: N={N} particles, one of {_lib.PF_PARTICLES} expected")
-    if not (_lib.PS_MIN_PATHS <= M <= N and M & (M - 1) == 0):
-        raise _lib.VissmError(f"sv_smooth: M={M} trajectories, a power of two in {_lib.PS_MIN_PATHS} .. N = {N} "
-                              "expected")
-    if K > 65535:
-        raise _lib.VissmError(f"sv_smooth: K={K} filters, at most 65535 per call")
-    dev = theta.device
-    if cloud.device != dev:
-        raise _lib.VissmError("sv_smooth: all tensors on one device expected")
-    T_total = _sv_series("sv_smooth", obs, dev)
-    need = t0 + H + (1 if x_next is not None else 0)
-    if H < 1 or t0 < 0 or t0 + H >= 2 ** 31 or need > T_total:
-        raise _lib.VissmError(f"sv_smooth: bad horizon H={H} t0={t0}: every column with a next state reads "
-                              f"y[t0 + c + 2], up to y[{need}] of y[0 .. {T_total}]")
-    key, row = _key_and_row("sv_smooth", seed, row0)
-    theta = theta.contiguous()
-    if x_next is not None:
-        if not x_next.is_cuda or x_next.device != dev or x_next.dtype != torch.float32 or \
-                tuple(x_next.shape) != (K * M, 1) or not x_next.is_contiguous():
-            raise _lib.VissmError(f"sv_smooth: x_next: a contiguous fp32 GPU tensor [{K * M}, 1] expected")
-    paths = torch.empty(K * M, 1, H, dtype=torch.float32, device=dev)
-    x_first = torch.empty(K * M, 1, dtype=torch.float32, device=dev)
-    ix = torch.empty(K * M, H, dtype=torch.int32, device=dev) if idx else None
-    qt = torch.empty(K, H, M, N, dtype=torch.int64, device=dev) if trace else None
-    d = _lib.PsDesc(_lib.MODEL_SV, K, N, M, H, t0, float(dt))
-    check(_lib.load().vissm_sv_smooth(ctypes.byref(d), key, row, ptr(theta), ptr(cloud), ptr(obs), T_total,
-                                      ptr(x_next), ptr(paths), ptr(x_first), ptr(ix), ptr(qt),
-                                      _lib.stream_handle(dev)), "vissm_sv_smooth")
-    return ParticleSmoothResult(paths, x_first, ix, qt)
+    fn = "sv_smooth"
+
+    def series_of(dev, H, t0):
+        T_total = _sv_series(fn, obs, dev)
+        need = t0 + H + (1 if x_next is not None else 0)
+        return (ptr(obs), T_total), need <= T_total, (": every column with a next state reads y[t0 + c + 2], up to "
+                                                      f"y[{need}] of y[0 .. {T_total}]")
+
+    return _smooth(fn, "vissm_sv_smooth", _lib.MODEL_SV, 1, theta, cloud, dt, True, series_of, M, seed, row0, t0,
+                   x_next, idx, trace)
 
 
 # ---------------------------------------------------------------------------------------
@@ -1298,68 +1299,81 @@ def _adaptive_args(what: str, adapt_end, target_accept, gamma) -> tuple:
 
 
 def _pmmh_chain(what: str, sv: bool, model_id: int, theta_cur, ll_cur, chol, prior, x_start, obs, obs_bin, dt, obs_std,
-                N, n_iter, seed, row0, it0, trace: bool, adapt: Optional[tuple] = None):
-    """pmmh, sv_pmmh, pmmh_adaptive and sv_pmmh_adaptive: `what` is the function's name (vissm_<what> its C entry), sv
-    says whether the series is the stochastic-volatility model's y[0 .. T] (x_start is then h_start [1], obs_bin None
-    and obs_std unused), adapt is None (chol is prop_chol [P, P]) or (adapt_end, target_accept, gamma) (chol is
-    chol_in [C, P, P]).  The refusals of the C entry, by host arithmetic before any GPU call; then the outputs and the
-    launch."""
+                N, n_iter, seed, row0, it0, trace: bool, adapt: Optional[tuple] = None, cpm: Optional[tuple] = None):
+    """pmmh, sv_pmmh, pmmh_adaptive, sv_pmmh_adaptive and sv_cpmmh: `what` is the function's name (vissm_<what> its C
+    entry), sv says whether the series is the stochastic-volatility model's y[0 .. T] (x_start is then h_start [1],
+    obs_bin None and obs_std unused), adapt is None (chol is prop_chol [P, P]) or (adapt_end, target_accept, gamma)
+    (chol is chol_in [C, P, P]), cpm is None or the correlated chain's (rho, aux_n, aux_r, aux_sel) (with sv and
+    adapt).  The refusals of the C entry, by host arithmetic before any GPU call; then the outputs and the launch.
+    The correlated chain keeps the places and words of its own refusals: the series behind the GPU check, as
+    sv_filter_sorted refuses it (VissmError), with at least one transition; chol_in with the other tensors; the device
+    named with each tensor."""
+    exc = ValueError
     if not sv:
         if model_id == _lib.MODEL_SV:
-            raise ValueError(f"{what}: no observation model for SV (its first coordinate is the observed series)")
+            raise exc(f"{what}: no observation model for SV (its first coordinate is the observed series)")
         if model_id not in _lib.MODEL_S:
-            raise ValueError(f"{what}: unknown model {model_id}")
+            raise exc(f"{what}: unknown model {model_id}")
     S, P = _lib.MODEL_S[model_id], _lib.MODEL_P[model_id]
-    N, n_iter, it0 = int(N), int(n_iter), int(it0)
-    if N not in _lib.PF_PARTICLES:
-        raise ValueError(f"{what}: N={N} particles, one of {_lib.PF_PARTICLES} expected")
+    N, n_iter, it0 = _check_particles(what, exc, N), int(n_iter), int(it0)
     if sv:
-        if not 0.0 < float(dt) < float("inf"):
-            raise ValueError(f"{what}: dt must be positive and finite, got {dt}")
-    elif not 0.0 < float(obs_std) < float("inf"):
-        raise ValueError(f"{what}: a positive, finite obs_std expected, got {obs_std}")
+        _check_positive(what, exc, dt, "dt must be positive and finite")
+    else:
+        _check_positive(what, exc, obs_std, "a positive, finite obs_std expected")
+    if cpm is not None:
+        rho, aux_n, aux_r, aux_sel = float(cpm[0]), *cpm[1:]
+        if not 0.0 <= rho < 1.0 or not 0.0 <= float(torch.tensor(rho, dtype=torch.float32)) < 1.0:
+            raise exc(f"{what}: rho={rho} outside [0, 1) (as an fp32 value)")
     if theta_cur.dim() != 2 or theta_cur.shape[1] != P or theta_cur.shape[0] < 1:
-        raise ValueError(f"{what}: theta_cur [C >= 1, {P}] expected, got {tuple(theta_cur.shape)}")
+        raise exc(f"{what}: theta_cur [C >= 1, {P}] expected, got {tuple(theta_cur.shape)}")
     C = theta_cur.shape[0]
     if n_iter < 0 or it0 < 0 or it0 + n_iter >= 2 ** 31:
-        raise ValueError(f"{what}: bad iterations it0={it0} n_iter={n_iter}")
+        raise exc(f"{what}: bad iterations it0={it0} n_iter={n_iter}")
     if adapt is not None:
         adapt = _adaptive_args(what, *adapt)
     if sv:
-        if obs.dim() != 1 or obs.shape[0] < 1 or obs.dtype != torch.float32:
-            raise ValueError(f"{what}: obs: an fp32 vector y[0 .. T] expected, got {obs.dtype} {tuple(obs.shape)}")
-        T_total = obs.shape[0] - 1
-        if T_total >= 2 ** 31 - 1:
-            raise ValueError(f"{what}: T = {T_total} reaches 2^31 - 1")
+        if cpm is None:
+            if obs.dim() != 1 or obs.shape[0] < 1 or obs.dtype != torch.float32:
+                raise exc(f"{what}: obs: an fp32 vector y[0 .. T] expected, got {obs.dtype} {tuple(obs.shape)}")
+            T_total = obs.shape[0] - 1
+            if T_total >= 2 ** 31 - 1:
+                raise exc(f"{what}: T = {T_total} reaches 2^31 - 1")
         series, shaped = [obs], [("h_start", x_start, (1,))]
     else:
         if obs.dim() != 2 or obs.shape[0] != S or obs_bin.shape != obs.shape:
-            raise ValueError(f"{what}: obs and obs_bin [{S}, T] expected, got {tuple(obs.shape)} and "
-                             f"{tuple(obs_bin.shape)}")
+            raise exc(f"{what}: obs and obs_bin [{S}, T] expected, got {tuple(obs.shape)} and {tuple(obs_bin.shape)}")
         T_total = obs.shape[1]
         if T_total * S >= 2 ** 31:
-            raise ValueError(f"{what}: T S = {T_total} * {S} reaches 2^31")
+            raise exc(f"{what}: T S = {T_total} * {S} reaches 2^31")
         series = [obs, obs_bin]
         shaped = [("x_start", x_start, (S,)), ("obs", obs, (S, T_total)), ("obs_bin", obs_bin, (S, T_total))]
-    if not 0 <= int(row0) < 2 ** 64:
-        raise ValueError(f"{what}: row0={row0} outside [0, 2^64)")
+    key, row = _key_and_row(what, seed, row0, exc)
     if adapt is None:  # (prop_chol takes its turn below)
         shaped = [("prop_chol", chol, (P, P)), ("prior", prior, (P, 2))] + shaped
-    else:
+    elif cpm is None:
         if chol.dtype != torch.float32 or tuple(chol.shape) != (C, P, P):
-            raise ValueError(f"{what}: fp32 chol_in {[C, P, P]} expected, got {chol.dtype} {tuple(chol.shape)}")
+            raise exc(f"{what}: fp32 chol_in {[C, P, P]} expected, got {chol.dtype} {tuple(chol.shape)}")
         shaped = [("prior", prior, (P, 2))] + shaped
+    else:
+        shaped = [("chol_in", chol, (C, P, P)), ("prior", prior, (P, 2))] + shaped
     _require_gpu(theta_cur, chol, prior, x_start, *series)
-    for name, x, shape in [("theta_cur", theta_cur, (C, P))] + shaped:
-        if x.dtype != torch.float32 or tuple(x.shape) != shape:
-            raise ValueError(f"{what}: fp32 {name} {list(shape)} expected, got {x.dtype} {tuple(x.shape)}")
     dev = theta_cur.device
-    if not ll_cur.is_cuda or ll_cur.dtype != torch.float64 or tuple(ll_cur.shape) != (C,) or \
-            not ll_cur.is_contiguous():
-        raise ValueError(f"{what}: ll_cur: a contiguous float64 GPU tensor [{C}] expected")
+    if cpm is not None:
+        T_total = _sv_series(what, obs, dev)
+        if T_total < 1 or T_total >= 2 ** 31 - 1:
+            raise exc(f"{what}: T = {T_total}: at least one transition, fewer than 2^31 - 1 expected")
+    on_dev = " on one device" if cpm is not None else ""
+    for name, x, shape in [("theta_cur", theta_cur, (C, P))] + shaped:
+        if x.dtype != torch.float32 or tuple(x.shape) != shape or (on_dev and x.device != dev):
+            raise exc(f"{what}: fp32 {name} {list(shape)}{on_dev} expected, got {x.dtype} {tuple(x.shape)}")
+    _check_layout(what, exc, "ll_cur", ll_cur, (C,), torch.float64, dev if on_dev else None)
     if any(t.device != dev for t in (ll_cur, chol, prior, x_start, *series)):
-        raise ValueError(f"{what}: all tensors on one device expected")
-    key, row = ctypes.c_uint64(seed & (2 ** 64 - 1)), ctypes.c_uint64(int(row0))
+        raise exc(f"{what}: all tensors on one device expected")
+    if cpm is not None:
+        _cpm_aux(what, aux_n, aux_r, (C, 2), T_total, N, dev)
+        _check_layout(what, exc, "aux_sel", aux_sel, (C,), torch.int32, dev)
+        if bool(((aux_sel != 0) & (aux_sel != 1)).any()):
+            raise exc(f"{what}: aux_sel holds a value other than 0 and 1")
     f32, f64 = torch.float32, torch.float64
     e = lambda *shape, dtype=f32: torch.empty(*shape, dtype=dtype, device=dev)
     t = lambda *shape, dtype=f32: e(*shape, dtype=dtype) if trace else None
@@ -1371,7 +1385,11 @@ def _pmmh_chain(what: str, sv: bool, model_id: int, theta_cur, ll_cur, chol, pri
         chol_end = e(C, P, P)
         more = [t(C, n_iter, 8), t(C, n_iter, dtype=f64), t(C, n_iter, dtype=f64), t(C, n_iter, P, P)]
         scalars, out = adapt, chain + [chol_end] + traces + more
-        result = PmmhAdaptiveResult(*chain, *traces, chol_end, *more)
+        if cpm is None:
+            result = PmmhAdaptiveResult(*chain, *traces, chol_end, *more)
+        else:
+            scalars += (ctypes.c_float(rho), ptr(aux_n), ptr(aux_r), ptr(aux_sel))
+            result = CpmmhResult(*chain, *traces, chol_end, *more, aux_sel)
     d = _lib.PmmhDesc(model_id, C, N, n_iter, it0, T_total, float(dt), float(obs_std))
     entry = "vissm_" + what
     check(getattr(_lib.load(), entry)(ctypes.byref(d), key, row, *map(ptr, (theta_cur, ll_cur, chol, prior, x_start)),
@@ -1488,26 +1506,19 @@ def sv_filter_sorted(theta: torch.Tensor, x_start: torch.Tensor, obs: torch.Tens
     aux_n(t, j): sv_filter's filter with a sort before the scan, so that nearby aux give nearby estimates.  x_start:
     [K N] or one value.  cloud: also h after each move [K, T, N]; trace: also the sorted states, the integer weights,
     the ancestors and U.  Nothing is drawn: two calls are bitwise equal."""
-    N = int(N)
-    if N not in _lib.PF_PARTICLES:
-        raise ValueError(f"sv_filter_sorted: N={N} particles, one of {_lib.PF_PARTICLES} expected")
-    if not 0.0 < float(dt) < float("inf"):
-        raise ValueError(f"sv_filter_sorted: dt must be positive and finite, got {dt}")
+    fn, exc = "sv_filter_sorted", ValueError
+    N = _check_particles(fn, exc, N)
+    _check_positive(fn, exc, dt, "dt must be positive and finite")
     _require_gpu(theta, x_start)
     if theta.dtype != torch.float32 or x_start.dtype != torch.float32 or theta.dim() != 2 or theta.shape[1] != 4:
-        raise ValueError(f"sv_filter_sorted: fp32 theta [K, 4] and x_start expected, got {tuple(theta.shape)}")
+        raise exc(f"{fn}: fp32 theta [K, 4] and x_start expected, got {tuple(theta.shape)}")
     K, dev = theta.shape[0], theta.device
-    if K * N >= 2 ** 31:
-        raise ValueError(f"sv_filter_sorted: K N = {K} * {N} reaches 2^31")
-    if x_start.numel() == 1:
-        x_start = x_start.reshape(1).expand(K * N).contiguous()
-    if x_start.numel() != K * N or x_start.device != dev:
-        raise ValueError(f"sv_filter_sorted: x_start [{K * N}] (or one value) on theta's device expected, got "
-                         f"{tuple(x_start.shape)}")
-    T = _sv_series("sv_filter_sorted", obs, dev)
+    _check_rows(fn, exc, K, N)
+    x_start = _sv_x_start(fn, exc, x_start, K * N, dev)
+    T = _sv_series(fn, obs, dev)
     if T < 1:
-        raise ValueError("sv_filter_sorted: a series of at least one transition expected")
-    _cpm_aux("sv_filter_sorted", aux_n, aux_r, (K,), T, N, dev)
+        raise exc(f"{fn}: a series of at least one transition expected")
+    _cpm_aux(fn, aux_n, aux_r, (K,), T, N, dev)
     e = lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, device=dev)
     loglik, ll_inc = e(K, dtype=torch.float64), e(K, T)
     cl = e(K, T, N) if cloud else None
@@ -1561,53 +1572,6 @@ def sv_cpmmh(theta_cur: torch.Tensor, ll_cur: torch.Tensor, chol_in: torch.Tenso
     adapt_end = 0 is the fixed-proposal chain with the factors chol_in [C, 4, 4].  A call with it0' = it0 + n_iter,
     theta_end, ll_end, chol_end and the same three aux tensors continues bitwise.  Every other argument, the outputs
     and the traces are sv_pmmh_adaptive's; the result also holds aux_sel (the same tensor)."""
-    what, P = "sv_cpmmh", 4
-    N, n_iter, it0, rho = int(N), int(n_iter), int(it0), float(rho)
-    if N not in _lib.PF_PARTICLES:
-        raise ValueError(f"{what}: N={N} particles, one of {_lib.PF_PARTICLES} expected")
-    if not 0.0 < float(dt) < float("inf"):
-        raise ValueError(f"{what}: dt must be positive and finite, got {dt}")
-    if not 0.0 <= rho < 1.0 or not 0.0 <= float(torch.tensor(rho, dtype=torch.float32)) < 1.0:
-        raise ValueError(f"{what}: rho={rho} outside [0, 1) (as an fp32 value)")
-    if theta_cur.dim() != 2 or theta_cur.shape[1] != P or theta_cur.shape[0] < 1:
-        raise ValueError(f"{what}: theta_cur [C >= 1, {P}] expected, got {tuple(theta_cur.shape)}")
-    C = theta_cur.shape[0]
-    if n_iter < 0 or it0 < 0 or it0 + n_iter >= 2 ** 31:
-        raise ValueError(f"{what}: bad iterations it0={it0} n_iter={n_iter}")
-    adapt = _adaptive_args(what, adapt_end, target_accept, gamma)
-    if not 0 <= int(row0) < 2 ** 64:
-        raise ValueError(f"{what}: row0={row0} outside [0, 2^64)")
-    _require_gpu(theta_cur, chol_in, prior, h_start, obs)
-    dev = theta_cur.device
-    T = _sv_series(what, obs, dev)
-    if T < 1 or T >= 2 ** 31 - 1:
-        raise ValueError(f"{what}: T = {T}: at least one transition, fewer than 2^31 - 1 expected")
-    for name, x, shape in (("theta_cur", theta_cur, (C, P)), ("chol_in", chol_in, (C, P, P)), ("prior", prior, (P, 2)),
-                           ("h_start", h_start, (1,))):
-        if x.dtype != torch.float32 or tuple(x.shape) != shape or x.device != dev:
-            raise ValueError(f"{what}: fp32 {name} {list(shape)} on one device expected, got {x.dtype} "
-                             f"{tuple(x.shape)}")
-    if not ll_cur.is_cuda or ll_cur.dtype != torch.float64 or tuple(ll_cur.shape) != (C,) or \
-            not ll_cur.is_contiguous() or ll_cur.device != dev:
-        raise ValueError(f"{what}: ll_cur: a contiguous float64 GPU tensor [{C}] expected")
-    _cpm_aux(what, aux_n, aux_r, (C, 2), T, N, dev)
-    if not aux_sel.is_cuda or aux_sel.device != dev or aux_sel.dtype != torch.int32 or \
-            tuple(aux_sel.shape) != (C,) or not aux_sel.is_contiguous():
-        raise ValueError(f"{what}: aux_sel: a contiguous int32 GPU tensor [{C}] expected")
-    if bool(((aux_sel != 0) & (aux_sel != 1)).any()):
-        raise ValueError(f"{what}: aux_sel holds a value other than 0 and 1")
-    key, row = ctypes.c_uint64(seed & (2 ** 64 - 1)), ctypes.c_uint64(int(row0))
-    f32, f64 = torch.float32, torch.float64
-    e = lambda *shape, dtype=f32: torch.empty(*shape, dtype=dtype, device=dev)
-    t = lambda *shape, dtype=f32: e(*shape, dtype=dtype) if trace else None
-    chain = [e(C, n_iter, P), e(C, n_iter, dtype=f64), e(C, n_iter, dtype=torch.int32), e(C, P), e(C, dtype=f64)]
-    traces = [t(C, n_iter, P), t(C, n_iter, dtype=f64), t(C, n_iter, dtype=f64)]
-    chol_end = e(C, P, P)
-    more = [t(C, n_iter, 8), t(C, n_iter, dtype=f64), t(C, n_iter, dtype=f64), t(C, n_iter, P, P)]
-    d = _lib.PmmhDesc(_lib.MODEL_SV, C, N, n_iter, it0, T, float(dt), 0.0)
-    check(_lib.load().vissm_sv_cpmmh(ctypes.byref(d), key, row, *map(ptr, (theta_cur, ll_cur, chol_in, prior, h_start,
-                                                                             obs)), *adapt, ctypes.c_float(rho),
-                                     ptr(aux_n), ptr(aux_r), ptr(aux_sel),
-                                     *map(ptr, chain + [chol_end] + traces + more), _lib.stream_handle(dev)),
-          "vissm_sv_cpmmh")
-    return CpmmhResult(*chain, *traces, chol_end, *more, aux_sel)
+    return _pmmh_chain("sv_cpmmh", True, _lib.MODEL_SV, theta_cur, ll_cur, chol_in, prior, h_start, obs, None, dt, 0.0,
+                       N, n_iter, seed, row0, it0, trace, (adapt_end, target_accept, gamma),
+                       (rho, aux_n, aux_r, aux_sel))
